@@ -2,8 +2,8 @@
 """Benchmark of the reranker scoring hot path on MI355X (BASELINE.json metric:
 query-doc pairs scored/sec at 1/2/4/8 GPUs).
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
-    python bench.py --gpus N --steps K --warmup W        (no rank environment: starts its own N ranks, benchlib/launch.py)
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
+    python bench.py --gpus N --steps K --warmup W       (no rank environment: starts its own N ranks, benchlib/launch.py)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +15,11 @@ rank scores its own 64 queries per step; `--scaling strong`: the step's queries 
 over the ranks) and each step ends with one RCCL all-gather of the score vectors.
 Rank 0 prints ONE JSON line.
 
-What the line carries (N = 1, default model):
+A plain run sets up, warms up (W untimed steps, then the K steps replayed untimed until the warm-up has lasted 0.25 s:
+benchlib/common.py timed_loop), times exactly K steps, writes the last step's scores if --dump-outputs DIR is given, and prints
+the line: value / ms_per_step of those K steps.  Everything below is measured only with --full.
+
+What the line carries with --full (N = 1, default model):
   value / ms_per_step  KNRM on Zipf(1.1) term ids (the headline leg), consecutive steps score DIFFERENT batches
   roofline             HBM fraction of the KNRM kernel, from a leg where HBM is the binding resource (uniform ids over a table
                        far larger than the 256 MB Infinity Cache): bytes the kernel REQUESTS / kernel time / 8 TB/s, <= 1 by
@@ -40,7 +44,7 @@ from benchlib import launch  # noqa: E402
 from benchlib.bert import bench_bert  # noqa: E402
 from benchlib.common import Ctx, _tables, default_queries  # noqa: E402
 from benchlib.interaction import InteractionLeg, interaction_record  # noqa: E402
-from benchlib.report import emit  # noqa: E402
+from benchlib.report import dump_outputs, emit  # noqa: E402
 from benchlib.siblings import bench_sibling  # noqa: E402
 
 
@@ -49,9 +53,17 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline steps, run everything else the benchmark measures and checks: the repetitions of the timed steps "
+                         "(--repeats 5), the serial-step, resident, uniform-id and qlen-8 legs, the DRMM / BERT / sibling legs, roofline and per-pass "
+                         "figures, the PMC traffic child runs, the oracle checks, the CPU baselines, the other BERT operand type.  Without it a run "
+                         "sets up, warms up, times exactly --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy (float32; the scores of "
+                         "the step, all ranks' after the all-gather; a seeded sample of at most 16 M values if larger)")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the K timed steps are run this many times inside the invocation (warm-up once); value / ms_per_step are the median repetition's, "
-                         "the others are reported under `repeats`")
+                         "the others are reported under `repeats` (default 1; 5 with --full)")
     ap.add_argument("--model", default="knrm", choices=["knrm", "drmm", "bert", "drmmtks", "pacrr", "convknrm"],
                     help="knrm (default, BASELINE.json's metric) | drmm | bert | the row-N4 siblings drmmtks, pacrr, convknrm")
     ap.add_argument("--queries", type=int, default=0, help="queries per step per GPU (0 = 64 for the interaction models - 250 for drmm, configs[2] - and 1 for bert)")
@@ -100,7 +112,12 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-also", action="store_true", help="skip the DRMM / BERT legs of the default invocation")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs in the CPU baseline sample (0 = auto)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:      # a plain run: the headline's timed steps only
+        args.no_also = args.no_cpu_baseline = args.no_roofline_leg = args.no_pmc_traffic = args.no_pass_times = args.no_bert_other_dtype = True
+    return args
 
 
 def main():
@@ -110,12 +127,14 @@ def main():
     if os.environ.get("CAPAMD_LIB_PATH"):       # an A/B build of the library (scripts/build_variant*.sh): it has no profiling twin
         args.no_pass_times = True
     ctx = Ctx(args)
+    outputs = {}      # the timed path's last step, filled by the headline leg (benchlib/report.py: dump_outputs)
     if args.model == "bert":
-        rec = bench_bert(args, ctx, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline)
+        rec = bench_bert(args, ctx, args.steps, args.warmup, with_cpu=not args.no_cpu_baseline, outputs=outputs)
     elif args.model in ("drmmtks", "pacrr", "convknrm"):
-        rec = bench_sibling(args, ctx)
+        rec = bench_sibling(args, ctx, outputs=outputs)
     else:
-        rec = interaction_record(args, ctx, args.model, args.steps, args.warmup, args.queries or default_queries(args.model), with_cpu=not args.no_cpu_baseline)
+        rec = interaction_record(args, ctx, args.model, args.steps, args.warmup, args.queries or default_queries(args.model), with_cpu=not args.no_cpu_baseline,
+                                 outputs=outputs)
         default_line = args.model == "knrm" and ctx.world == 1 and not args.no_also and not args.uniform_ids and not args.launch_docs and not args.resident
         if default_line and ctx.rank == 0:
             # the other two north-star models, timed by the same driver run (short legs; their own roofline / cpu_baseline)
@@ -183,6 +202,8 @@ def main():
                 torch.cuda.empty_cache()
     ctx.close()
     if ctx.rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         emit(rec)
 
 

@@ -42,8 +42,9 @@ def bert_queries(n_docs_per_query, qids, P, S, VOCAB, dev):
     return {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
 
 
-def bench_bert(args, ctx, steps, warmup, with_cpu):
+def bench_bert(args, ctx, steps, warmup, with_cpu, outputs=None):
     """BASELINE.json configs[3]: BERT-base MaxP, 4 passages x 256 tokens per document, 1000 docs/query.
+    `outputs`, when given, receives the document scores of the last timed step (all ranks' after the all-gather).
     `--scaling strong --queries Q`: configs[4]'s shape - the step's Q queries (1000 candidates each, generator seeded 1000 + qid)
     are divided over the ranks in contiguous blocks, one all_gather of the document scores per step."""
     from types import SimpleNamespace
@@ -87,29 +88,32 @@ def bench_bert(args, ctx, steps, warmup, with_cpu):
     engine.status_word(dev).raise_if_set()
     assert torch.isfinite(out[0]).all()
     scores = out[0].clone()
+    if outputs is not None:
+        outputs["scores"] = (gathered if use_dist else scores).cpu().numpy()
 
     # dominant kernel: the FFN1 GEMM (folded LayerNorm + bias + GELU epilogue), timed by HIP events around each of its launches
     # (capamd_debug_ffn1_timing, capreolus_amd/csrc/capamd_profiling.h - a hook of the -DCAPAMD_PROFILING build of the library only, so
     # the timed steps above ran the product library) in one more step of the same batch, run strictly serially (kernels of concurrent
     # streams would stretch each other's durations)
     tot_ms, launches, rows = ctypes.c_double(0), ctypes.c_int64(0), ctypes.c_int64(0)
-    with _lib.profiling_build() as lib:
-        eng.n_streams = 1
-        step(0)                       # (sizes the single-stream workspace; module load of the second library)
-        torch.cuda.synchronize(dev)
-        lib.capamd_debug_ffn1_timing(1)
-        step(0)
-        torch.cuda.synchronize(dev)
-        assert torch.equal(out[0], scores), "the serial and the multi-stream step disagree"
-        eng.n_streams = max(1, args.bert_streams)
-        _lib.check(lib.capamd_debug_ffn1_timing_read(ctypes.byref(tot_ms), ctypes.byref(launches), ctypes.byref(rows)), "ffn1 timing")
-        lib.capamd_debug_ffn1_timing(0)
+    if args.full:
+        with _lib.profiling_build() as lib:
+            eng.n_streams = 1
+            step(0)                       # (sizes the single-stream workspace; module load of the second library)
+            torch.cuda.synchronize(dev)
+            lib.capamd_debug_ffn1_timing(1)
+            step(0)
+            torch.cuda.synchronize(dev)
+            assert torch.equal(out[0], scores), "the serial and the multi-stream step disagree"
+            eng.n_streams = max(1, args.bert_streams)
+            _lib.check(lib.capamd_debug_ffn1_timing_read(ctypes.byref(tot_ms), ctypes.byref(launches), ctypes.byref(rows)), "ffn1 timing")
+            lib.capamd_debug_ffn1_timing(0)
     serial = False
     out[0] = scores
     gemm_s = tot_ms.value * 1e-3 / max(1, launches.value)
     gemm_tf = 2.0 * rows.value * F * H / (tot_ms.value * 1e-3) / 1e12 if tot_ms.value > 0 else 0.0
     Mg = rows.value // max(1, launches.value)
-    coll = collective_info(ctx, docs)       # (every rank takes part)
+    coll = collective_info(ctx, docs, timed=args.full)       # (every rank takes part)
     if rank != 0:
         return None
     psg_per_s = docs * P * world * steps / elapsed
@@ -173,5 +177,7 @@ def bench_bert(args, ctx, steps, warmup, with_cpu):
                                "sample": f"{n} document(s) ({n * P} passages) through oracle/bert_port.py (fp32 ATen ops, {min(cores, 64)} threads); the timed "
                                          f"GPU scores of these documents agree with it to {err:.1e}"}
         torch.set_num_threads(cores)
+    if not args.full:      # a plain run: no figure beyond the timed steps (the FFN1 kernel was not timed)
+        rec["roofline"] = None
     return rec
 

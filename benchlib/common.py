@@ -72,17 +72,39 @@ class Ctx:
             self.dist.destroy_process_group()
 
 
+WARM_S = 0.25      # least duration of a warm-up (timed_loop)
+
+
 def timed_loop(ctx, step, warmup, steps, drain=None):
     """W untimed steps, then exactly K steps between two fences (barrier + synchronize on both sides); wall clock = max over ranks.
     ONE HIP event pair on the launch stream brackets the K steps: (event time / K) is the per-step device time and can never
     exceed the wall-clock step.  (Event pairs around every single launch - what round 1 did - put a system-scope release /
     acquire between consecutive kernels, which drops the table rows the previous launch left in L2: those launches ran 7-10 %
-    slower than the back-to-back launches of the timed loop, hence a `kernel_ms` above `ms_per_step` in BENCH_r01.)"""
+    slower than the back-to-back launches of the timed loop, hence a `kernel_ms` above `ms_per_step` in BENCH_r01.)
+    With W > 0 the warm-up then goes on with more untimed steps until it has lasted WARM_S: the chip reaches its steady rate only
+    after ~30 ms of back-to-back steps (in five repetitions of a 10 ms window the first ran 3-6 % slower and the second 1-2 %,
+    profiles/r06/bench_full_*.json), so a short W alone would time the ramp.  The extra steps come in chunks sized from the last
+    chunk's step time to the warm-up time left, so the warm-up ends near WARM_S whatever K is; every rank runs the same chunks
+    (times are maxima over ranks).  They cycle through the window's own step indices, so the timed steps score the same batches."""
+    t0 = time.perf_counter()
     for i in range(warmup):
         step(i)
     if drain:
         drain()
     ctx.fence()
+    spent = ctx.max_over_ranks(time.perf_counter() - t0)
+    per_step, j = spent / max(1, warmup), 0       # (the first steps carry the set-up: an overestimate, never an overshoot)
+    while warmup and spent < WARM_S:
+        n = max(1, int((WARM_S - spent) / per_step))
+        t1 = time.perf_counter()
+        for _ in range(n):
+            step(warmup + j % steps)
+            j += 1
+        if drain:
+            drain()
+        ctx.fence()
+        per_step = ctx.max_over_ranks(time.perf_counter() - t1) / n
+        spent = ctx.max_over_ranks(time.perf_counter() - t0)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     ev0.record()
@@ -96,14 +118,19 @@ def timed_loop(ctx, step, warmup, steps, drain=None):
     return elapsed, ev0.elapsed_time(ev1) * 1e-3 / steps
 
 
-def collective_info(ctx, floats_per_rank):
+def collective_info(ctx, floats_per_rank, timed=True):
     """What the N > 1 line says about its one collective: the backend and the number of ranks the process group really has (so that a
-    SCALE record proves N ranks took part), the bytes one step gathers, and the duration of that all_gather on its own (10 blocking
-    repetitions after a fence; inside the timed steps it runs asynchronously under the next step's scoring)."""
+    SCALE record proves N ranks took part), the bytes one step gathers, and with `timed` (bench.py --full) the duration of that
+    all_gather on its own (10 blocking repetitions after a fence; inside the timed steps it runs asynchronously under the next step's
+    scoring)."""
     if not ctx.use_dist:
         return None
     dist, dev = ctx.dist, ctx.dev
     world = dist.get_world_size()
+    rec = {"backend": dist.get_backend(), "rccl_ranks": world, "collective": "all_gather_into_tensor (fp32 scores)",
+           "gathered_bytes_per_step": floats_per_rank * world * 4}
+    if not timed:
+        return rec
     src = torch.zeros(floats_per_rank, dtype=torch.float32, device=dev)
     dst = torch.empty(floats_per_rank * world, dtype=torch.float32, device=dev)
     for _ in range(2):
@@ -113,9 +140,36 @@ def collective_info(ctx, floats_per_rank):
     for _ in range(10):
         dist.all_gather_into_tensor(dst, src)
     torch.cuda.synchronize()
-    ms = ctx.max_over_ranks(time.perf_counter() - t0) * 100.0
-    return {"backend": dist.get_backend(), "rccl_ranks": world, "collective": "all_gather_into_tensor (fp32 scores)", "gathered_bytes_per_step": floats_per_rank * world * 4,
-            "gather_ms": ms}
+    rec["gather_ms"] = ctx.max_over_ranks(time.perf_counter() - t0) * 100.0
+    return rec
+
+
+def candidate_lists(*args, **kwargs):
+    """synthetic.make_candidate_list_torch with PyTorch's deterministic algorithms on, so that the same arguments give the same
+    batch in every run: its query-term injection scatters five writes per document, two of which can hit the same position, and
+    the default GPU scatter lets either of them win (2-6 of 64,000 benchmark scores changed between runs); the deterministic
+    scatter keeps the last.  One op of the generator has no deterministic form in torch's list, the cumsum of the Zipf CDF (a scan:
+    the same bits in every run so far), so torch is asked to warn instead of raising (warn_only); that alert is the only one let
+    through - any other op without a deterministic form raises here."""
+    import warnings
+
+    from capreolus_amd import synthetic
+
+    mode, warn_only = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter("always")
+            batch = synthetic.make_candidate_list_torch(*args, **kwargs)
+    finally:
+        torch.use_deterministic_algorithms(mode, warn_only=warn_only)
+    for w in caught:
+        text = str(w.message)
+        if "deterministic" in text and not text.startswith("cumsum"):
+            raise RuntimeError(f"the benchmark's input generator ran an op with no deterministic form: {text}")
+        if "deterministic" not in text:
+            warnings.warn_explicit(w.message, w.category, w.filename, w.lineno)
+    return batch
 
 
 _tables = {}

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))      # the repository root (bench.py lives there)
-from benchlib.common import Ctx1, F32_PEAK_TFLOPS, GATHER_CEILING_GBS, L2_PEAK_GBS, HBM_PEAK_GBS, KERNEL_EVAL_PEAK_G, KERNEL_EVAL_PEAK_SOURCE, KERNEL_VARIANT, SIMS_LIMITER, SIMS_PIPE, _tables, algorithmic_bytes_per_pair, collective_info, default_queries, kernel_of, repeated_timed_loop, table
+from benchlib.common import Ctx1, F32_PEAK_TFLOPS, GATHER_CEILING_GBS, L2_PEAK_GBS, HBM_PEAK_GBS, KERNEL_EVAL_PEAK_G, KERNEL_EVAL_PEAK_SOURCE, KERNEL_VARIANT, SIMS_LIMITER, SIMS_PIPE, _tables, algorithmic_bytes_per_pair, candidate_lists, collective_info, default_queries, kernel_of, repeated_timed_loop, table
 from benchlib.cpu import cpu_baseline
 
 
@@ -20,7 +20,7 @@ class InteractionLeg:
     def __init__(self, args, ctx, model, V, uniform, n_queries, nb, seed0, zero_idf=False):
         from types import SimpleNamespace
 
-        from capreolus_amd import engine, synthetic
+        from capreolus_amd import engine
         from capreolus_amd.reranker import DRMM, KNRM
 
         self.args, self.ctx, self.model, self.V, self.uniform = args, ctx, model, V, uniform
@@ -30,7 +30,7 @@ class InteractionLeg:
         self.emb = table(dev, V, self.D)
         self.batches = []
         for b in range(nb):
-            batch = synthetic.make_candidate_list_torch(n_queries, args.docs, V, dev, seed=seed0 + 1000 * b, maxqlen=self.Q, maxdoclen=self.L,
+            batch = candidate_lists(n_queries, args.docs, V, dev, seed=seed0 + 1000 * b, maxqlen=self.Q, maxdoclen=self.L,
                                                         uniform_ids=uniform)
             if model == "drmm":
                 batch["query"] = batch["query"].clamp(min=0)
@@ -417,38 +417,11 @@ def lists_roofline(model, headline, hbm_leg, n_pairs, dev_s, compulsory, traffic
     return out
 
 
-def interaction_record(args, ctx, model, steps, warmup, n_queries, with_cpu):
-    """One KNRM / DRMM measurement: headline leg + HBM roofline leg (+ CPU baseline on rank 0 at N = 1)."""
+def leg_figures(args, ctx, leg, model, steps, dev_s, serial):
+    """`bench.py --full`: the cache-level rates of the timed leg (`headline`), the per-pass figures of the list route and the HBM-bound
+    roofline leg with its PMC traffic (`roof`, None when neither is measured).  Returns (roof, headline)."""
     Q, L, D = getattr(args, "qlen", 4), 800, args.dim
     world = ctx.world
-    strong = args.scaling == "strong"
-    per_rank_q = n_queries // world if strong else n_queries
-    if strong and n_queries % world:
-        raise SystemExit("--scaling strong needs --queries divisible by the number of GPUs")
-    nb = max(1, args.batches if model == "knrm" else min(args.batches, 2))      # (a DRMM batch is 250,000 pairs = 1.6 GB of id rows)
-    leg = InteractionLeg(args, ctx, model, args.vocab, args.uniform_ids, per_rank_q, nb, 1 + ctx.rank)
-    elapsed, dev_s = leg.run(warmup, steps, args.repeats)
-    serial = None
-    if leg.step_side and world == 1:
-        # the same steps strictly one after the other on ONE stream (what the line reported before round 6's step streams): the call's
-        # own duration - the per-pass figures of `roofline` belong to this form
-        sides, leg.step_side = leg.step_side, []
-        s_elapsed, s_dev, s_rep = repeated_timed_loop(ctx, leg.step, 2, steps, None, 3)
-        leg.step_side = sides
-        serial = {"value": leg.n_pairs * steps / s_elapsed, "unit": "pairs/s", "ms_per_step": 1e3 * s_elapsed / steps, "call_ms": s_dev * 1e3,
-                  "ms_per_step_min": s_rep["ms_per_step_min"], "ms_per_step_max": s_rep["ms_per_step_max"],
-                  "what": "bench.py --step-streams 1: every step's call waits for the previous one (3 repetitions of the K steps, median)"}
-    zero_idf = None
-    if model == "drmm" and world == 1 and not args.uniform_ids:
-        # configs[2]'s second run (SURVEY 8(d)): the same lists with the all-zero idf rows EmbedText produces by default
-        z = InteractionLeg(args, ctx, model, args.vocab, args.uniform_ids, per_rank_q, 1, 1 + ctx.rank, zero_idf=True)
-        z_elapsed, _ = z.run(2, max(3, steps // 2))
-        z_err = z.check_against_oracle(min(64, z.n_pairs))[2]       # (the timed scores of its last step against the C oracle)
-        zero_idf = {"value": z.n_pairs * max(3, steps // 2) / z_elapsed, "unit": "pairs/s", "ms_per_step": 1e3 * z_elapsed / max(3, steps // 2),
-                    "steps": max(3, steps // 2), "query_idf": "all zeros (EmbedText without an idf table, extractor/embedtext.py:86-96)",
-                    "oracle_check": z_err}
-        del z
-        torch.cuda.empty_cache()
     n_pairs = leg.n_pairs
     req_b, nonpad, distinct = leg.bytes_requested_per_pair()
     abytes = algorithmic_bytes_per_pair(model, Q, L, D)
@@ -545,6 +518,49 @@ def interaction_record(args, ctx, model, steps, warmup, n_queries, with_cpu):
         if not args.no_pmc_traffic and ctx.rank == 0 and not args.uniform_ids:
             traffic, traffic_src = pmc_traffic(args, model, "lists")
         roof = lists_roofline(model, headline, roof, n_pairs, serial["call_ms"] * 1e-3 if serial else dev_s, compulsory, traffic, traffic_src)
+    return roof, headline
+
+
+def interaction_record(args, ctx, model, steps, warmup, n_queries, with_cpu, outputs=None):
+    """One KNRM / DRMM measurement: headline leg (+ with --full: HBM roofline leg, CPU baseline on rank 0 at N = 1).  `outputs`, when given,
+    receives the scores of the last timed step (all ranks' after the all-gather)."""
+    Q, L, D = getattr(args, "qlen", 4), 800, args.dim
+    world = ctx.world
+    strong = args.scaling == "strong"
+    per_rank_q = n_queries // world if strong else n_queries
+    if strong and n_queries % world:
+        raise SystemExit("--scaling strong needs --queries divisible by the number of GPUs")
+    nb = max(1, args.batches if model == "knrm" else min(args.batches, 2))      # (a DRMM batch is 250,000 pairs = 1.6 GB of id rows)
+    leg = InteractionLeg(args, ctx, model, args.vocab, args.uniform_ids, per_rank_q, nb, 1 + ctx.rank)
+    elapsed, dev_s = leg.run(warmup, steps, args.repeats)
+    if outputs is not None:
+        outputs["scores"] = (leg.gathered[leg.last_gather] if ctx.use_dist else leg.out).cpu().numpy()
+    serial = None
+    if args.full and leg.step_side and world == 1:
+        # the same steps strictly one after the other on ONE stream (what the line reported before round 6's step streams): the call's
+        # own duration - the per-pass figures of `roofline` belong to this form
+        sides, leg.step_side = leg.step_side, []
+        s_elapsed, s_dev, s_rep = repeated_timed_loop(ctx, leg.step, 2, steps, None, 3)
+        leg.step_side = sides
+        serial = {"value": leg.n_pairs * steps / s_elapsed, "unit": "pairs/s", "ms_per_step": 1e3 * s_elapsed / steps, "call_ms": s_dev * 1e3,
+                  "ms_per_step_min": s_rep["ms_per_step_min"], "ms_per_step_max": s_rep["ms_per_step_max"],
+                  "what": "bench.py --step-streams 1: every step's call waits for the previous one (3 repetitions of the K steps, median)"}
+    zero_idf = None
+    if args.full and model == "drmm" and world == 1 and not args.uniform_ids:
+        # configs[2]'s second run (SURVEY 8(d)): the same lists with the all-zero idf rows EmbedText produces by default
+        z = InteractionLeg(args, ctx, model, args.vocab, args.uniform_ids, per_rank_q, 1, 1 + ctx.rank, zero_idf=True)
+        z_elapsed, _ = z.run(2, max(3, steps // 2))
+        z_err = z.check_against_oracle(min(64, z.n_pairs))[2]       # (the timed scores of its last step against the C oracle)
+        zero_idf = {"value": z.n_pairs * max(3, steps // 2) / z_elapsed, "unit": "pairs/s", "ms_per_step": 1e3 * z_elapsed / max(3, steps // 2),
+                    "steps": max(3, steps // 2), "query_idf": "all zeros (EmbedText without an idf table, extractor/embedtext.py:86-96)",
+                    "oracle_check": z_err}
+        del z
+        torch.cuda.empty_cache()
+    n_pairs = leg.n_pairs
+    launches = len(leg.slices)
+    roof = headline = None
+    if args.full:
+        roof, headline = leg_figures(args, ctx, leg, model, steps, dev_s, serial)
     total_pairs = n_pairs * world
     rec = {
         "metric": "query-doc pairs scored/sec",
@@ -565,7 +581,8 @@ def interaction_record(args, ctx, model, steps, warmup, n_queries, with_cpu):
             "workload": f"{model.upper()} inference (BASELINE.json configs[{1 if model == 'knrm' else 2}]): qlen={Q} dlen={L} "
                         f"embed={D} vocab={args.vocab}, {args.docs} docs/query x {per_rank_q} queries per step per GPU, "
                         f"{'uniform' if args.uniform_ids else 'Zipf(1.1)'} term ids, lognormal doc lengths, "
-                        + (f"scored as whole candidate lists ({distinct_per_list:.0f} distinct terms per list), " if leg.lists else "") +
+                        + ("scored as whole candidate lists" + (f" ({headline['mean_distinct_terms_per_list']:.0f} distinct terms per list)" if headline else "") + ", "
+                           if leg.lists else "") +
                         f"{launches} launch(es) per step" + (f" round-robin over {len(leg.side)} HIP streams" if leg.side else "") + (", replayed as one captured HIP graph" if leg.graphs else "") +
                         (f", consecutive steps round-robin over {len(leg.step_side)} HIP streams (step i + 1's passes overlap step i's)" if leg.step_side else "") +
                         f", {len(leg.batches)} distinct batches in rotation"
@@ -573,8 +590,9 @@ def interaction_record(args, ctx, model, steps, warmup, n_queries, with_cpu):
             "pairs_per_step_per_gpu": n_pairs,
             "parallelism": f"query-sharded x{world}, one all_gather of scores per step (asynchronous, under the next step's scoring)" if world > 1 else "single GPU",
         },
-        "roofline": roof if roof is not None else {"bound": "hbm", "kernel": KERNEL_VARIANT[model], "achieved": None, "peak": HBM_PEAK_GBS,
-                                                   "unit": "GB/s", "frac": None, "traffic": None, "headline_leg": headline},
+        # (a plain run: None - nothing beyond the timed steps is measured)
+        "roofline": roof if (roof is not None or headline is None) else {"bound": "hbm", "kernel": KERNEL_VARIANT[model], "achieved": None, "peak": HBM_PEAK_GBS,
+                                                                         "unit": "GB/s", "frac": None, "traffic": None, "headline_leg": headline},
     }
     if serial is not None:
         rec["step_streams"] = {"streams": len(leg.step_side), "serial_steps": serial,
@@ -585,7 +603,7 @@ def interaction_record(args, ctx, model, steps, warmup, n_queries, with_cpu):
     if zero_idf is not None:
         rec["zero_idf_run"] = zero_idf
     if ctx.use_dist:
-        rec["collective"] = collective_info(ctx, n_pairs)
+        rec["collective"] = collective_info(ctx, n_pairs, timed=args.full)
     if with_cpu and world == 1:
         rec["cpu_baseline"] = cpu_baseline(args, model, leg.check_against_oracle, leg)
     return rec

@@ -120,6 +120,21 @@ def compact(rec, full_path):
     return line
 
 
+DUMP_LIMIT = 1 << 24      # values per array written by --dump-outputs (64 MB of float32 in all with one array)
+
+
+def dump_outputs(directory, outputs):
+    """`bench.py --dump-outputs DIR`: every array the timed path returned in its last step as DIR/<name>.npy in float32, so that two
+    builds can be compared output for output on the same seeded inputs.  An array of more than DUMP_LIMIT values is written as the
+    values at a fixed, seeded, sorted sample of DUMP_LIMIT flat indices."""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.asarray(a, dtype=np.float32).ravel()
+        if a.size > DUMP_LIMIT:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_LIMIT, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def emit(rec):
     """The whole record goes to bench_full.json (next to this file; `also` legs in full, CPU sweeps, per-pass work figures, notes) and to
     stderr; stdout gets ONE compact JSON line (<= 4 KB) - the last line of stdout: RCCL prints a version banner through C stdio, which

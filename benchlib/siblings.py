@@ -8,16 +8,17 @@ import time
 import numpy as np
 import torch
 
-from benchlib.common import Ctx1, HBM_PEAK_GBS, SIMS_PIPE, _tables, algorithmic_bytes_per_pair, table, timed_loop
+from benchlib.common import Ctx1, HBM_PEAK_GBS, SIMS_PIPE, _tables, algorithmic_bytes_per_pair, candidate_lists, table, timed_loop
 from benchlib.interaction import lists_roofline
 
 
-def sibling_leg(args, ctx, model, V, uniform, steps, warmup, seed):
+def sibling_leg(args, ctx, model, V, uniform, steps, warmup, seed, outputs=None):
     """One timed leg of a row-N4 model on candidate lists of the KNRM benchmark's shape: (reranker module, batch, last scores, wall
-    seconds, per-step device seconds, bytes of one gathered row, mean non-pad terms per document)."""
+    seconds, per-step device seconds, bytes of one gathered row, mean non-pad terms per document).  `outputs`, when given, receives the
+    scores of the last timed step (all ranks' after the all-gather)."""
     from types import SimpleNamespace
 
-    from capreolus_amd import engine, synthetic
+    from capreolus_amd import engine
     from capreolus_amd.reranker import DRMMTKS, PACRR, ConvKNRM
 
     world, dev, use_dist, dist = ctx.world, ctx.dev, ctx.use_dist, ctx.dist
@@ -25,7 +26,7 @@ def sibling_leg(args, ctx, model, V, uniform, steps, warmup, seed):
     n_queries = args.queries or 64
     n_pairs = n_queries * args.docs
     emb = table(dev, V, D)
-    batch = synthetic.make_candidate_list_torch(n_queries, args.docs, V, dev, seed=seed, maxqlen=Q, maxdoclen=L, uniform_ids=uniform)
+    batch = candidate_lists(n_queries, args.docs, V, dev, seed=seed, maxqlen=Q, maxdoclen=L, uniform_ids=uniform)
     if model == "convknrm":      # nn.Embedding ids only (the slowembedtext extractor has no negative OOV ids)
         batch = {k: (v.abs() if v.dtype == torch.int64 else v) for k, v in batch.items()}
     torch.manual_seed(0)
@@ -79,6 +80,8 @@ def sibling_leg(args, ctx, model, V, uniform, steps, warmup, seed):
     torch.cuda.synchronize()
     assert os.environ.get("CAPAMD_BENCH_NOCHECK") == "1" or torch.isfinite(out[0]).all()   # (the knob: profiling builds that drop a phase of the kernel)
     status.__exit__(None, None, None)
+    if outputs is not None:
+        outputs["scores"] = (gathered if use_dist else out[0]).cpu().numpy()
     nonpad = float((d_all > 0).sum().item()) / n_pairs
     passes = None
     if as_lists and not args.no_pass_times:       # the route's passes, HIP events between them (the -DCAPAMD_PROFILING build of the same kernels)
@@ -129,10 +132,10 @@ def sibling_oracle(model, m, D, q, d, idf, emb_h):
                                    sd["combine.0.bias"])
 
 
-def bench_sibling(args, ctx, model=None, steps=None, warmup=None, with_cpu=None, check_pairs=256):
+def bench_sibling(args, ctx, model=None, steps=None, warmup=None, with_cpu=None, check_pairs=256, outputs=None):
     """Row N4 models on the KNRM benchmark's candidate lists: DRMM-TKS, PACRR (KNRM's gather; same algorithmic bytes) and
-    ConvKNRM (per position 6 projection-table parts of `filters` floats instead of one embedding row).  The timed
-    scores of the first `check_pairs` pairs are checked against the C oracle in every run; `roofline.frac` comes from a second leg
+    ConvKNRM (per position 6 projection-table parts of `filters` floats instead of one embedding row).  With --full the
+    timed scores of the first `check_pairs` pairs are checked against the C oracle; `roofline.frac` comes from a second leg
     on uniform ids over the `--roofline-vocab` table (where HBM binds), like the KNRM / DRMM lines."""
     model = model or args.model
     steps = steps or args.steps
@@ -142,7 +145,8 @@ def bench_sibling(args, ctx, model=None, steps=None, warmup=None, with_cpu=None,
     Q, L, V, D = 4, 800, args.vocab, args.dim
     n_queries = args.queries or 64
     n_pairs = n_queries * args.docs
-    rr, m, batch, scores, elapsed, kern_s, row, nonpad, as_lists, passes, n_streams = sibling_leg(args, ctx, model, V, args.uniform_ids, steps, warmup, 1 + rank)
+    rr, m, batch, scores, elapsed, kern_s, row, nonpad, as_lists, passes, n_streams = sibling_leg(args, ctx, model, V, args.uniform_ids, steps, warmup, 1 + rank,
+                                                                                                         outputs)
     q_all, d_all, idf_all = batch["query"], batch["posdoc"], batch["query_idf"]
     emb = table(dev, V, D)
     if model == "convknrm":
@@ -157,7 +161,7 @@ def bench_sibling(args, ctx, model=None, steps=None, warmup=None, with_cpu=None,
     if rank != 0:
         return None
     # the timed scores are the oracle's (a bounded sample; oracle/ is the checker here, never the thing measured)
-    emb_h = emb.cpu().numpy() if V <= 400001 else None
+    emb_h = emb.cpu().numpy() if (args.full and V <= 400001) else None      # (a plain run checks nothing beyond the timed steps)
     oracle_err = None
     if emb_h is not None and os.environ.get("CAPAMD_BENCH_NOCHECK") != "1":
         nchk = min(check_pairs, n_pairs)

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 model=knrm
 case "${1:-}" in knrm|drmm) model=$1; shift;; esac
 ( CAPAMD_KNRM_STREAM=2 CAPAMD_DRMM_STREAM=2 timeout 900 python -m pytest tests/test_gpu_parity.py -q -x -k "knrm or KNRM or drmm or DRMM or random_geometries or full_size or resident or permut" 2>&1 | tail -8 ) > gpurun_out/stream_parity.log 2>&1; tail -3 gpurun_out/stream_parity.log
-B="python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-pmc-traffic --model $model"
+B="python $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-pmc-traffic --model $model"
 for round in 1 2; do
   for spec in "$@"; do
     name=${spec%%[:@]*}; envs=""; lib=""

@@ -9,7 +9,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py -q -x -k "lists" 2>&1 | ta
 for model in knrm drmm; do
   for round in 1 2; do
     for mode in lists pairs; do
-      extra=""; [ $mode = pairs ] && extra="--per-pair"
+      extra="--full"; [ $mode = pairs ] && extra="--full --per-pair"
       timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-also --no-pmc-traffic --no-roofline-leg --model $model $extra 2>gpurun_out/lists_err.txt | tail -1 > gpurun_out/ab_$mode.json
       python - <<PY
 import json

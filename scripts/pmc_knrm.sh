@@ -12,7 +12,7 @@ for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_I
          "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_REQUEST_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_STALL_INFLIGHT_MAX_sum" \
          "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum"; do
   i=$((i+1))
-  timeout 200 rocprofv3 --pmc $C --output-format csv -d /tmp/pmc_$TAG/$i -o p -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline $EXTRA > /dev/null 2>&1
+  timeout 200 rocprofv3 --pmc $C --output-format csv -d /tmp/pmc_$TAG/$i -o p -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $EXTRA > /dev/null 2>&1
 done
 python3 - <<PY > $R/gpurun_out/pmc_$TAG.txt
 import csv, glob, collections

@@ -43,14 +43,14 @@ def _check_line(rec, n_gpus, scaling):
 
 
 def test_bench_knrm_weak_leg_over_rccl():
-    rec = _run_bench(["--steps", "3", "--warmup", "1", "--queries", "8", "--no-cpu-baseline", "--no-also", "--no-roofline-leg", "--no-pmc-traffic"])
+    rec = _run_bench(["--full", "--steps", "3", "--warmup", "1", "--queries", "8", "--no-cpu-baseline", "--no-also", "--no-roofline-leg", "--no-pmc-traffic"])
     _check_line(rec, 1, "weak")
     assert rec["collective"]["gathered_bytes_per_step"] == 8 * 1000 * 4
 
 
 def test_bench_bert_strong_leg_over_rccl():
     """BASELINE configs[4]'s shape (queries in contiguous blocks over the ranks, one gather of the document scores) on one rank."""
-    rec = _run_bench(["--model", "bert", "--scaling", "strong", "--queries", "1", "--docs", "64", "--steps", "1", "--warmup", "1",
+    rec = _run_bench(["--full", "--model", "bert", "--scaling", "strong", "--queries", "1", "--docs", "64", "--steps", "1", "--warmup", "1",
                       "--no-cpu-baseline", "--no-bert-other-dtype"])
     _check_line(rec, 1, "strong")
     assert "configs[4]" in rec["config"]["workload"]
@@ -58,9 +58,9 @@ def test_bench_bert_strong_leg_over_rccl():
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs (the single-GPU box covers the same path with one rank)")
 def test_bench_two_ranks_over_rccl():
-    rec = _run_bench(["--steps", "3", "--warmup", "1", "--queries", "8", "--no-cpu-baseline", "--no-also", "--no-roofline-leg", "--no-pmc-traffic"], nproc=2)
+    rec = _run_bench(["--full", "--steps", "3", "--warmup", "1", "--queries", "8", "--no-cpu-baseline", "--no-also", "--no-roofline-leg", "--no-pmc-traffic"], nproc=2)
     _check_line(rec, 2, "weak")
-    rec = _run_bench(["--model", "bert", "--scaling", "strong", "--queries", "2", "--docs", "32", "--steps", "1", "--warmup", "1",
+    rec = _run_bench(["--full", "--model", "bert", "--scaling", "strong", "--queries", "2", "--docs", "32", "--steps", "1", "--warmup", "1",
                       "--no-cpu-baseline", "--no-bert-other-dtype"], nproc=2)
     _check_line(rec, 2, "strong")
 
@@ -115,7 +115,7 @@ def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with no rank environment (how the driver's record of round 5 invoked it): bench.py re-executes itself under
     torch.distributed.run (benchlib/launch.py) and rank 0's JSON line says two RCCL ranks took part."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--queries", "8"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--queries", "8"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     rec = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
