@@ -33,6 +33,17 @@ class BertModel(ctypes.Structure):
 
 _mp = ctypes.POINTER(BertModel)
 
+
+class ParadeHeadModel(ctypes.Structure):
+    """capamd_parade_head_model (include/capreolus_amd.h)."""
+
+    _fields_ = [("initial_cls", ctypes.c_void_p), ("pos_emb", ctypes.c_void_p), ("layer1", ctypes.c_void_p * 16), ("layer2", ctypes.c_void_p * 16),
+                ("linear_w", ctypes.c_void_p), ("linear_b", ctypes.c_void_p), ("hidden", ctypes.c_int), ("heads", ctypes.c_int), ("ffn", ctypes.c_int),
+                ("ln_eps", ctypes.c_float)]
+
+
+_hp = ctypes.POINTER(ParadeHeadModel)
+
 # name -> (restype, argtypes); must list every symbol include/capreolus_amd.h declares
 SIGNATURES = {
     "capamd_version": (_i, []),
@@ -82,6 +93,9 @@ SIGNATURES = {
     "capamd_bert_maxp_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _mp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "capamd_cedr_passage_features": (_i, [_vp, _vp, _vp, _i, _i, _i, _mp, _i64, _vp, _i64, _i, _vp, ctypes.POINTER(_i), _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "capamd_cedr_score": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "capamd_parade_workspace_bytes": (_i64, [_hp, _i, _i]),
+    "capamd_parade_passage_cls": (_i, [_vp, _vp, _vp, _i, _i, _i, _mp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "capamd_parade_head": (_i, [_vp, _i, _i, _hp, _vp, _i64, _vp, _vp, _vp]),
     "capamd_maxp_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "capamd_bert_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "capamd_bert_gemm_ln": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

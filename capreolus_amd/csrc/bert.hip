@@ -744,6 +744,33 @@ __global__ void cls_rows_kernel(const T* __restrict__ P, const float2* __restric
   for (int i = threadIdx.x; i < H; i += blockDim.x)
     out[psg * H + i] = (T)(((float)P[cm_offset(tok, i, H)] - st.x) * st.y * gamma[i] + (beta ? beta[i] : 0.f));
 }
+// PARADE's [CLS] rows: out[r][:] = LayerNorm(pre[r] + x[r]) in fp32 (the last LayerNorm of the [CLS]-row tail, as ln_kernel<2> computes
+// it, without rounding the result to the 16-bit type).  One wave per row, H % 64 == 0, H <= 1024.
+template <typename T>
+__global__ __launch_bounds__(256) void ln_rows_f32_kernel(const T* __restrict__ pre, const T* __restrict__ x, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, int64_t n, int H, float eps, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n) return;
+  const int nc = H >> 6;
+  float v[16];
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (i < nc) {
+      v[i] = (float)pre[r * H + lane + 64 * i] + (float)x[r * H + lane + 64 * i];
+      sum += v[i];
+    }
+  const float mean = wave_sum64(sum) / (float)H;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (i < nc) q += (v[i] - mean) * (v[i] - mean);
+  const float rstd = rsqrtf(wave_sum64(q) / (float)H + eps);
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (i < nc) out[r * H + lane + 64 * i] = (v[i] - mean) * rstd * gamma[lane + 64 * i] + beta[lane + 64 * i];
+}
 __global__ void neutral_stats_kernel(int64_t M, float* __restrict__ mu, float* __restrict__ rstd, float2* __restrict__ mr) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += (int64_t)gridDim.x * blockDim.x) {
     mu[i] = 0.f; rstd[i] = 1.f; mr[i] = make_float2(0.f, 1.f);
@@ -853,7 +880,8 @@ int64_t plan_microbatch(int64_t NP, int64_t cap, int S, int H, int F) {
 
 template <typename T>
 hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_t* seg, int64_t NP, int64_t mb, int S,
-                           const capamd_bert_model* m, const Workspace& w, int* status, hipStream_t s, const CedrTap* tap = nullptr) {
+                           const capamd_bert_model* m, const Workspace& w, int* status, hipStream_t s, const CedrTap* tap = nullptr,
+                           float* cls_out = nullptr) {
   const int H = m->hidden, F = m->ffn;
   const T* blob = (const T*)m->blob;
   const float eps = m->ln_eps > 0.f ? m->ln_eps : kLnEps;
@@ -946,6 +974,12 @@ hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_
           g.N = H; g.K = F; g.A = mid_c; g.W = w2; g.bias = b2; g.out_bf16 = pre_c;
           e = launch_gemm<kEpiBiasBf16, T>(g, s);
           if (e != hipSuccess) break;
+          if (cls_out) {   // PARADE: the [CLS] rows of the last hidden state in fp32, straight from the last LayerNorm (no pooler)
+            hipLaunchKernelGGL(ln_rows_f32_kernel<T>, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, s, (const T*)pre_c, (const T*)x_c, ln2g, ln2b, np, H, eps,
+                               cls_out + p0 * H);
+            cls_done = true;
+            break;
+          }
           hipLaunchKernelGGL((ln_kernel<2, T>), dim3((unsigned)((npad + 3) / 4)), dim3(256), 0, s, (const T*)pre_c, nullptr, nullptr, nullptr, nullptr, nullptr,
                              0, 0, 1, ln2g, ln2b, npad, H, x_c, status, 0, eps, -1, 0);
           cls_done = true;
@@ -985,6 +1019,13 @@ hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_
         if (tap) cedr_tap_layer<T>(*tap, l + 1, (const T*)w.xb, mask_mb, seg_mb, p0, np, S, H, s, true, (const float2*)w.mr_x, ln2g, ln2b);
       }
       if (e != hipSuccess) break;
+      if (cls_out) {   // (CAPAMD_BERT_CLS_TAIL=0 only: the tail above wrote them otherwise)
+        if (!cls_done)
+          hipLaunchKernelGGL(cedr_cls_rows_cm_kernel<T>, dim3((unsigned)np), dim3(256), 0, s, (const T*)w.xb, (const float2*)w.mr_x, last_g, last_b, S, H,
+                             cls_out + p0 * H);
+        e = hipGetLastError();
+        continue;
+      }
       if (tap) {   // the [CLS] rows of the last hidden state (CEDRKNRM.py:160), LayerNorm applied on the way
         hipLaunchKernelGGL(cedr_cls_rows_cm_kernel<T>, dim3((unsigned)np), dim3(256), 0, s, (const T*)w.xb, (const float2*)w.mr_x, last_g, last_b, S, H,
                            tap->cls + p0 * H);
@@ -1041,8 +1082,8 @@ hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_
       if (tap) cedr_tap_layer<T>(*tap, l + 1, (const T*)w.xb, mask_mb, seg_mb, p0, np, S, H, s);
     }
     if (e != hipSuccess) break;
-    if (tap) {   // CEDR-KNRM reads the [CLS] rows of the last hidden state itself (CEDRKNRM.py:160); no pooler / classifier
-      hipLaunchKernelGGL(cedr_cls_rows_kernel<T>, dim3((unsigned)np), dim3(256), 0, s, (const T*)w.xb, S, H, tap->cls + p0 * H);
+    if (tap || cls_out) {   // CEDR-KNRM / PARADE read the [CLS] rows of the last hidden state themselves (CEDRKNRM.py:160, ptparade.py:74)
+      hipLaunchKernelGGL(cedr_cls_rows_kernel<T>, dim3((unsigned)np), dim3(256), 0, s, (const T*)w.xb, S, H, (tap ? tap->cls : cls_out) + p0 * H);
       e = hipGetLastError();
       continue;
     }
@@ -1211,6 +1252,27 @@ int capamd_cedr_passage_features(const int64_t* ids, const int64_t* mask, const 
   CedrTap tap{maxqlen + 1, K, n_layers, simmat_layers, mu, sigma, query_mask0, passage_kernel_sums, cls_rows, NP};
   const hipError_t e = (m->compute_dtype == 1) ? encode_passages<_Float16>(ids, mask, seg, NP, mb, S, m, w, status, s, &tap)
                                                 : encode_passages<__bf16>(ids, mask, seg, NP, mb, S, m, w, status, s, &tap);
+  if (e != hipSuccess) return CAPAMD_ERR_LAUNCH;
+  return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
+}
+
+int capamd_parade_passage_cls(const int64_t* ids, const int64_t* mask, const int64_t* seg, int B, int P, int S, const capamd_bert_model* m,
+                              int64_t passages_per_microbatch, void* workspace, int64_t workspace_bytes, float* cls_rows, int* status,
+                              void* stream) {
+  if (!ids || !mask || !seg || !dims_ok(m) || !workspace || !cls_rows || !status || B < 0 || P < 1) return CAPAMD_ERR_ARG;
+  if (B == 0) return CAPAMD_OK;
+  if (!supported_length(S) || S > m->max_pos || passages_per_microbatch < 1) return CAPAMD_ERR_ARG;
+  if (!m->word_emb || !m->pos_emb || !m->type_emb || !m->emb_ln_g || !m->emb_ln_b || !m->blob || !m->layer_f32) return CAPAMD_ERR_ARG;
+  const int H = m->hidden, F = m->ffn;
+  const int64_t NP = (int64_t)B * P;
+  const int64_t mb = plan_microbatch(NP, passages_per_microbatch, S, H, F);
+  if ((int64_t)ws_bytes_for(H, F, S, mb, NP) > workspace_bytes) return CAPAMD_ERR_WORKSPACE;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return CAPAMD_ERR_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  (void)hipGetLastError();
+  Workspace w = carve((char*)workspace, H, F, S, mb, NP);
+  const hipError_t e = (m->compute_dtype == 1) ? encode_passages<_Float16>(ids, mask, seg, NP, mb, S, m, w, status, s, nullptr, cls_rows)
+                                                : encode_passages<__bf16>(ids, mask, seg, NP, mb, S, m, w, status, s, nullptr, cls_rows);
   if (e != hipSuccess) return CAPAMD_ERR_LAUNCH;
   return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
 }

@@ -1255,3 +1255,125 @@ class CedrEngine:
         if check:
             status_word(dev).raise_if_set()
         return (out, feats) if return_features else out
+
+
+PARADE_MAX_PASSAGES = 63     # P + 1 rows per document in the aggregation head's attention (csrc/parade.hip)
+
+
+class ParadeEngine:
+    """PARADE (reference ptparade.py, aggregation = "transformer") on top of a BertEngine's packed encoder: capamd_parade_passage_cls
+    (encoder; the last layer on the [CLS] rows only; fp32 [CLS] rows of the last hidden state) followed by capamd_parade_head (the two
+    BertLayers over [initial_cls; passage rows] + position embeddings, then `linear`, in fp32)."""
+
+    def __init__(self, bert_engine, ln_eps=1e-12):
+        self.be = bert_engine
+        self.ln_eps = float(ln_eps)
+        self._wss = {}
+        self._streams = {}
+        self._head_ws = None
+
+    def _passages(self, ids, mask, seg, S, cls, ws_key):
+        """One capamd_parade_passage_cls call over n passages of length S ([n, S] x3) on the current stream."""
+        m, lib = self.be.model(), _lib.load()
+        n = ids.shape[0]
+        mb = min(self.be.microbatch * max(1, 256 // S), n)
+        need = lib.capamd_bert_workspace_bytes(ctypes.byref(m), S, mb, n)
+        if need < 0:
+            raise ValueError(f"unsupported passage length {S} (supported: multiples of 32 up to 256, 384, 512)")
+        ws = self._wss.get(ws_key)
+        if ws is None or ws.numel() < need or ws.device != ids.device:
+            ws = self._wss[ws_key] = torch.empty(need, dtype=torch.uint8, device=ids.device)
+        rc = lib.capamd_parade_passage_cls(_ptr(ids), _ptr(mask), _ptr(seg), n, 1, S, ctypes.byref(m), mb, _ptr(ws), ws.numel(), _ptr(cls),
+                                           _ptr(status_word(ids.device).t), _stream())
+        _lib.check(rc, "capamd_parade_passage_cls")
+
+    def passage_cls(self, ids, mask, seg, skip_padding=None):
+        """int64 [B, P, S] x3 -> fp32 [B * P, hidden]: the [CLS] rows of the last hidden state (ptparade.py:74).  skip_padding (default:
+        the encoder engine's setting): as in BertEngine.forward, every passage is encoded at the shortest supported length that holds
+        its last attended token (the rows are those of the full-length computation), the buckets on side streams; the rows are
+        scattered back by index_copy_."""
+        B, P, S = ids.shape
+        dev, NP = ids.device, B * P
+        H = self.be.model().hidden
+        cls = torch.empty((NP, H), dtype=torch.float32, device=dev)
+        fids, fmask, fseg = ids.view(NP, S), mask.view(NP, S), seg.view(NP, S)
+        if skip_padding is None:
+            skip_padding = self.be.skip_padding
+        lengths = [x for x in SUPPORTED_LENGTHS if x < S] if (skip_padding and S in SUPPORTED_LENGTHS) else []
+        if not lengths:
+            self._passages(fids, fmask, fseg, S, cls, None)
+            return cls
+        end = ((fmask != 0) * torch.arange(1, S + 1, device=dev)).amax(dim=1)
+        bounds = lengths + [S]
+        bucket = torch.bucketize(end, torch.tensor(lengths, device=dev), right=False)
+        order = torch.argsort(bucket, stable=True)
+        counts = torch.bincount(bucket, minlength=len(bounds)).cpu().tolist()   # the one host round trip of this call
+        main = torch.cuda.current_stream(dev)
+        lo, used = 0, []
+        for Sb, n in zip(bounds, counts):
+            if n == 0:
+                continue
+            sel = order[lo:lo + n]
+            lo += n
+            side = self._streams.get(Sb)
+            if side is None:
+                side = self._streams[Sb] = torch.cuda.Stream(device=dev)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                bi, bm, bs = (t.index_select(0, sel)[:, :Sb].contiguous() for t in (fids, fmask, fseg))
+                cls_b = torch.empty((n, H), dtype=torch.float32, device=dev)
+                self._passages(bi, bm, bs, Sb, cls_b, Sb)
+                cls.index_copy_(0, sel, cls_b)
+                for t in (bi, bm, bs, cls_b, sel):
+                    t.record_stream(side)
+            used.append(side)
+        for side in used:
+            main.wait_stream(side)
+        return cls
+
+    def head(self, cls, B, P, head_params, aggregated=False):
+        """capamd_parade_head over fp32 [B * P, hidden] [CLS] rows -> fp32 [B] (and the aggregated rows [B, hidden] if asked).
+        head_params: the PTParade_Class state_dict names (``initial_cls_embedding``, ``full_position_embeddings``,
+        ``transformer_layer_{1,2}.*``, ``linear.*``) -> live fp32 tensors on the device, read in place."""
+        lib = _lib.load()
+        keep = {k: _f32(v.detach()) for k, v in head_params.items()}
+        _need_gpu(cls, *keep.values())
+        H = keep["initial_cls_embedding"].numel()
+        if keep["full_position_embeddings"].numel() != (P + 1) * H:
+            raise ValueError(f"full_position_embeddings holds {keep['full_position_embeddings'].numel() // H} rows, the documents {P} passages + 1")
+        hm = _lib.ParadeHeadModel()
+        hm.initial_cls, hm.pos_emb = keep["initial_cls_embedding"].data_ptr(), keep["full_position_embeddings"].data_ptr()
+        for i, n in enumerate(_LAYER_TENSORS):
+            hm.layer1[i] = keep["transformer_layer_1." + n].data_ptr()
+            hm.layer2[i] = keep["transformer_layer_2." + n].data_ptr()
+        hm.linear_w, hm.linear_b = keep["linear.weight"].data_ptr(), keep["linear.bias"].data_ptr()
+        hm.hidden, hm.heads, hm.ffn, hm.ln_eps = H, H // 64, keep["transformer_layer_1.intermediate.dense.weight"].shape[0], self.ln_eps
+        need = lib.capamd_parade_workspace_bytes(ctypes.byref(hm), B, P)
+        if need < 0:
+            raise ValueError("unsupported PARADE geometry: need hidden == 64*heads <= 1024, ffn % 64 == 0, 1 <= passages <= 63")
+        dev = cls.device
+        if self._head_ws is None or self._head_ws.numel() < need or self._head_ws.device != dev:
+            self._head_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+        agg = torch.empty((B, H), dtype=torch.float32, device=dev) if aggregated else None
+        rc = lib.capamd_parade_head(_ptr(cls), B, P, ctypes.byref(hm), _ptr(self._head_ws), self._head_ws.numel(), _ptr(out), _ptr(agg), _stream())
+        _lib.check(rc, "capamd_parade_head")
+        return (out, agg) if aggregated else out
+
+    def forward(self, doc_input, doc_mask, doc_seg, head_params, return_cls=False, skip_padding=None, check=True):
+        """PTParade_Class.forward (reference ptparade.py:66-78): int64 [B, P, S] x3 -> fp32 [B] (and the fp32 [CLS] rows [B * P, hidden]
+        with return_cls).  The aggregation layers see every passage, the extractor's padding passages included (no passage mask)."""
+        B, P, S = doc_input.shape
+        if P < 1 or P > PARADE_MAX_PASSAGES:
+            raise ValueError(f"PARADE scores 1 to {PARADE_MAX_PASSAGES} passages per document (P + 1 <= 64 rows in the aggregation head); got {P}")
+        _need_gpu(doc_input, doc_mask, doc_seg)
+        ids, mask, seg = _i64(doc_input), _i64(doc_mask), _i64(doc_seg)
+        dev = ids.device
+        if B == 0:
+            out = torch.empty(0, dtype=torch.float32, device=dev)
+            return (out, torch.empty((0, self.be.model().hidden), device=dev)) if return_cls else out
+        cls = self.passage_cls(ids, mask, seg, skip_padding)
+        out = self.head(cls, B, P, head_params)
+        if check:
+            status_word(dev).raise_if_set()
+        return (out, cls) if return_cls else out

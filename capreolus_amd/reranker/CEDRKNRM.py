@@ -12,7 +12,7 @@ from torch import nn
 from .. import engine
 from . import Reranker
 from .KNRM import _RbfBank
-from .ptBERTMaxP import bert_body
+from .ptBERTMaxP import bert_body, encoder_from_hf
 
 
 class CEDRKNRM_Class(nn.Module):
@@ -57,22 +57,7 @@ class CEDRKNRM_Class(nn.Module):
 
     @staticmethod
     def _from_hf(name, hidden_dropout_prob):
-        """Reads a local/cached HF checkpoint (no network here) and copies its tensors into the container."""
-        from transformers import AutoModel
-
-        name = {"bert-base-msmarco": "Capreolus/bert-base-msmarco", "electra-base-msmarco": "Capreolus/electra-base-msmarco",
-                "electra-base": "google/electra-base-discriminator"}.get(name, name)      # the reference's aliases (CEDRKNRM.py:20-35)
-        hf = AutoModel.from_pretrained(name, hidden_dropout_prob=hidden_dropout_prob)
-        c = hf.config
-        # BERT, or ELECTRA whose embedding size equals its hidden size (no embeddings_project): the same encoder arithmetic
-        if c.model_type not in ("bert", "electra") or c.hidden_act != "gelu" or getattr(c, "embedding_size", c.hidden_size) != c.hidden_size:
-            raise NotImplementedError(f"{name}: unsupported architecture {c.model_type}/{c.hidden_act}")
-        body = bert_body(c.hidden_size, c.num_hidden_layers, c.num_attention_heads, c.intermediate_size, c.vocab_size,
-                         c.max_position_embeddings, c.type_vocab_size, pooler=c.model_type == "bert")
-        missing = body.load_state_dict(hf.state_dict(), strict=False)
-        if missing.missing_keys:
-            raise RuntimeError(f"checkpoint lacks {missing.missing_keys}")
-        return body
+        return encoder_from_hf(name, hidden_dropout_prob)
 
     def _params(self):
         p = {"bert." + k: v for k, v in self.bert.state_dict(keep_vars=True).items() if not k.endswith("position_ids")}

@@ -60,6 +60,26 @@ def bert_body(hidden=768, layers=12, heads=12, ffn=3072, vocab=30522, max_pos=51
     return body
 
 
+def encoder_from_hf(name, hidden_dropout_prob):
+    """A bare encoder (bert_body) filled from a local/cached HF checkpoint (no network here): BertModel checkpoints, and ElectraModel ones
+    whose embedding size equals the hidden size (the same encoder arithmetic without a pooler).  Shared by CEDR-KNRM and PARADE."""
+    from transformers import AutoModel
+
+    name = {"bert-base-msmarco": "Capreolus/bert-base-msmarco", "electra-base-msmarco": "Capreolus/electra-base-msmarco",
+            "electra-base": "google/electra-base-discriminator"}.get(name, name)      # the reference's aliases (CEDRKNRM.py:20-35)
+    hf = AutoModel.from_pretrained(name, hidden_dropout_prob=hidden_dropout_prob)
+    c = hf.config
+    # BERT, or ELECTRA whose embedding size equals its hidden size (no embeddings_project): the same encoder arithmetic
+    if c.model_type not in ("bert", "electra") or c.hidden_act != "gelu" or getattr(c, "embedding_size", c.hidden_size) != c.hidden_size:
+        raise NotImplementedError(f"{name}: unsupported architecture {c.model_type}/{c.hidden_act}")
+    body = bert_body(c.hidden_size, c.num_hidden_layers, c.num_attention_heads, c.intermediate_size, c.vocab_size,
+                     c.max_position_embeddings, c.type_vocab_size, pooler=c.model_type == "bert")
+    missing = body.load_state_dict(hf.state_dict(), strict=False)
+    if missing.missing_keys:
+        raise RuntimeError(f"checkpoint lacks {missing.missing_keys}")
+    return body
+
+
 def bert_container(hidden=768, layers=12, heads=12, ffn=3072, vocab=30522, max_pos=512, type_vocab=2):
     """Parameter tree of BertForSequenceClassification(num_labels=2) (state_dict names as HF)."""
     body = bert_body(hidden, layers, heads, ffn, vocab, max_pos, type_vocab)

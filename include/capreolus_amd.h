@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CAPAMD_VERSION 400
+#define CAPAMD_VERSION 401
 
 #define CAPAMD_OK 0
 #define CAPAMD_ERR_ARG 1       /* null pointer / bad size / unsupported configuration */
@@ -365,6 +365,38 @@ int capamd_cedr_passage_features(const int64_t* ids, const int64_t* mask, const 
 int capamd_cedr_score(const float* passage_kernel_sums, const float* cls_rows, int B, int P, int maxqlen, int n_layers, int K, int hidden,
                       int cls_mode, const float* w1, const float* b1, int combine_hidden, const float* w2, const float* b2, float* out,
                       float* features_out, void* stream);
+
+/* ---- PARADE (reference capreolus/reranker/ptparade.py, aggregation = "transformer") -----------------------------------------
+ * Replaces PTParade_Class.forward (:66-78, called from PTParade.test).  Two calls:
+ *  capamd_parade_passage_cls: runs the encoder (same model / workspace / micro-batch arguments as capamd_bert_maxp_forward; the
+ *   pooler and classifier pointers may be NULL) over all B*P passages and leaves cls_rows [B*P][hidden] = the [CLS] row of the last
+ *   hidden state in fp32 (:74, before any pooler).  The last layer is computed on the [CLS] rows only.
+ *  capamd_parade_head: the aggregation head (:53-65, 78) in fp32 throughout:
+ *   X0[b] = [initial_cls; cls_rows of document b] + pos_emb   ([P+1, hidden]),
+ *   X2 = BertLayer_2(BertLayer_1(X0)) (post-LN BERT layers, no attention mask, 1/sqrt(64) scaling, erf-GELU),
+ *   out[b] = linear_w . X2[b][0] + linear_b[0];  aggregated_out (optional) [B][hidden] = X2[b][0].
+ *   hidden = 64*heads <= 1024, ffn % 64 == 0, 1 <= P, P + 1 <= 64; tensors 16-byte aligned (CAPAMD_ERR_ALIGN otherwise).
+ * The parameters are read in place from the live fp32 tensors; layer1 / layer2 hold the 16 tensors of a BertLayer in the order of
+ * capamd_bert_pack_layer's first 16 (query, key, value, attention.output.dense, attention.output.LayerNorm, intermediate.dense,
+ * output.dense, output.LayerNorm; weight before bias). */
+typedef struct capamd_parade_head_model {
+  const float* initial_cls;  /* [hidden]          initial_cls_embedding */
+  const float* pos_emb;      /* [P + 1, hidden]   full_position_embeddings */
+  const float* layer1[16];   /* transformer_layer_1.* */
+  const float* layer2[16];   /* transformer_layer_2.* */
+  const float* linear_w;     /* [1, hidden]       linear.weight */
+  const float* linear_b;     /* [1]               linear.bias */
+  int hidden, heads, ffn;
+  float ln_eps;              /* the layers' LayerNorm epsilon (1e-12 for BERT and ELECTRA) */
+} capamd_parade_head_model;
+
+/* workspace for capamd_parade_head over B documents of P passages; -1 for an unsupported geometry (only the int fields are read) */
+int64_t capamd_parade_workspace_bytes(const capamd_parade_head_model* hm, int B, int P);
+int capamd_parade_passage_cls(const int64_t* ids, const int64_t* mask, const int64_t* seg, int B, int P, int S, const capamd_bert_model* m,
+                              int64_t passages_per_microbatch, void* workspace, int64_t workspace_bytes, float* cls_rows, int* status,
+                              void* stream);
+int capamd_parade_head(const float* cls_rows, int B, int P, const capamd_parade_head_model* hm, void* workspace, int64_t workspace_bytes,
+                       float* out, float* aggregated_out, void* stream);
 
 /* ---- ConvKNRM ------------------------------------------------------------------------
  * Replaces ConvKNRM_class.forward, capreolus/reranker/ConvKNRM.py:42-77 (called from ConvKNRM.test :112-116).
