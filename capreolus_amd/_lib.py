@@ -44,6 +44,22 @@ class ParadeHeadModel(ctypes.Structure):
 
 _hp = ctypes.POINTER(ParadeHeadModel)
 
+class TkLayer(ctypes.Structure):
+    """capamd_tk_layer (include/capreolus_amd.h)."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("wqkv", "bqkv", "wo", "bo", "ln1_g", "ln1_b", "w1", "b1", "w2", "b2", "ln2_g", "ln2_b")]
+
+
+class TkModel(ctypes.Structure):
+    """capamd_tk_model (include/capreolus_amd.h)."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("emb", "pe", "layers_host", "mixer", "s_log_w", "s_len_w", "comb_w")] + [
+        ("vocab", ctypes.c_int64), ("pad", ctypes.c_int64)] + [(n, ctypes.c_int) for n in ("dim", "heads", "ffdim", "numlayers", "max_len", "usemask")] + [
+        ("alpha", ctypes.c_float), ("ln_eps", ctypes.c_float)]
+
+
+_tp = ctypes.POINTER(TkModel)
+
 # name -> (restype, argtypes); must list every symbol include/capreolus_amd.h declares
 SIGNATURES = {
     "capamd_version": (_i, []),
@@ -96,6 +112,8 @@ SIGNATURES = {
     "capamd_parade_workspace_bytes": (_i64, [_hp, _i, _i]),
     "capamd_parade_passage_cls": (_i, [_vp, _vp, _vp, _i, _i, _i, _mp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "capamd_parade_head": (_i, [_vp, _i, _i, _hp, _vp, _i64, _vp, _vp, _vp]),
+    "capamd_tk_workspace_bytes": (_i64, [_tp, _i, _i, _i]),
+    "capamd_tk_forward": (_i, [_vp, _vp, _i, _i, _i, _tp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "capamd_maxp_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "capamd_bert_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "capamd_bert_gemm_ln": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

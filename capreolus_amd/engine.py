@@ -1377,3 +1377,127 @@ class ParadeEngine:
         if check:
             status_word(dev).raise_if_set()
         return (out, cls) if return_cls else out
+
+
+TK_WORKSPACE_BUDGET = 1 << 30      # bytes of activations per capamd_tk_forward call (documents run in micro-batches that fit)
+
+
+def _up64(n):
+    return (n + 63) // 64 * 64
+
+
+class TKEngine:
+    """TK (reference TK.py, TK_class.forward) through capamd_tk_forward.  The encoder's weights are re-laid out once per set of weights
+    into the padded layout of include/capreolus_amd.h (each head in its own 16-multiple slot, widths padded to 64 with zeros), kept
+    until any parameter changes (storage pointers + version counters, as ConvProjectionTables); the embedding table and the `pe`
+    buffer are read in place.  `docs_per_microbatch` (None: as many as TK_WORKSPACE_BUDGET holds) bounds the activations of a call."""
+
+    def __init__(self, docs_per_microbatch=None):
+        self.docs_per_microbatch = docs_per_microbatch
+        self._key = None
+        self._keep = None
+        self._ws = None
+
+    @staticmethod
+    def _layer_names(n):
+        pre = f"transformer_encoder.layers.{n}."
+        return [pre + s for s in ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight", "self_attn.out_proj.bias",
+                                  "norm1.weight", "norm1.bias", "linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias",
+                                  "norm2.weight", "norm2.bias")]
+
+    def _pack(self, params, heads, numlayers):
+        """the padded per-layer tensors (a list of 12 per layer, in capamd_tk_layer's order) and the TkLayer host array"""
+        D = params["embedding.weight"].shape[1]
+        F = params[self._layer_names(0)[6]].shape[0]
+        hd = D // heads
+        hs = (hd + 15) // 16 * 16
+        Dp, Fp, Hs = _up64(D), _up64(F), _up64(heads * hs)
+        dev = params["embedding.weight"].device
+        j = torch.arange(hd, device=dev)
+        h = torch.arange(heads, device=dev)
+        dst_h = (h[:, None] * hs + j[None, :]).reshape(-1)          # head slot columns / rows
+        src_h = (h[:, None] * hd + j[None, :]).reshape(-1)
+        dst_qkv = torch.cat([p * Hs + dst_h for p in range(3)])
+        src_qkv = torch.cat([p * D + src_h for p in range(3)])
+
+        def vec(t, n):
+            out = torch.zeros(n, dtype=torch.float32, device=dev)
+            out[: t.numel()] = t.reshape(-1)
+            return out
+
+        def mat(t, rows, cols):
+            out = torch.zeros(rows, cols, dtype=torch.float32, device=dev)
+            out[: t.shape[0], : t.shape[1]] = t
+            return out
+
+        tensors, layers = [], (_lib.TkLayer * numlayers)()
+        for n in range(numlayers):
+            in_w, in_b, out_w, out_b, g1, b1n, w1, b1, w2, b2, g2, b2n = (_f32(params[k].detach()) for k in self._layer_names(n))
+            wqkv = torch.zeros(3 * Hs, Dp, dtype=torch.float32, device=dev)
+            wqkv[dst_qkv, :D] = in_w[src_qkv]
+            bqkv = torch.zeros(3 * Hs, dtype=torch.float32, device=dev)
+            bqkv[dst_qkv] = in_b[src_qkv]
+            wo = torch.zeros(Dp, Hs, dtype=torch.float32, device=dev)
+            wo[:D, dst_h] = out_w[:, src_h]
+            ts = [wqkv, bqkv, wo, vec(out_b, Dp), vec(g1, Dp), vec(b1n, Dp), mat(w1, Fp, Dp), vec(b1, Fp), mat(w2, Dp, Fp), vec(b2, Dp),
+                  vec(g2, Dp), vec(b2n, Dp)]
+            ts = [t.contiguous() for t in ts]
+            for name, t in zip(_lib.TkLayer._fields_, ts):
+                setattr(layers[n], name[0], t.data_ptr())
+            tensors += ts
+        return tensors, layers
+
+    def model(self, params, heads, numlayers, usemask, alpha, pad, ln_eps, mixer=None):
+        """the capamd_tk_model of these live parameters (packing the encoder again only when a parameter changed)"""
+        names = [k for n in range(numlayers) for k in self._layer_names(n)]
+        _need_gpu(*(params[k] for k in names))
+        key = tuple((params[k].data_ptr(), params[k]._version) for k in names) + (heads, numlayers)
+        if key != self._key:
+            self._keep = self._pack(params, heads, numlayers)
+            self._key = key
+        tensors, layers = self._keep
+        emb, pe = _f32(params["embedding.weight"].detach()), _f32(params["position_encoder.pe"].detach())
+        heads_w = [_f32(params[k].detach()).reshape(-1) for k in ("s_log_fcc.weight", "s_len_fcc.weight", "comb_fcc.weight")]
+        mix = None if mixer is None else _f32(mixer.detach()).reshape(-1)
+        _need_gpu(emb, pe, *heads_w)
+        m = _lib.TkModel()
+        m.emb, m.pe, m.layers_host = emb.data_ptr(), pe.data_ptr(), ctypes.cast(layers, ctypes.c_void_p)
+        m.mixer = None if mix is None else mix.data_ptr()
+        m.s_log_w, m.s_len_w, m.comb_w = (t.data_ptr() for t in heads_w)
+        m.vocab, m.pad = emb.shape[0], int(pad)
+        m.dim, m.heads, m.ffdim, m.numlayers = emb.shape[1], int(heads), params[self._layer_names(0)[6]].shape[0], int(numlayers)
+        m.max_len, m.usemask, m.alpha, m.ln_eps = pe.shape[0], int(bool(usemask)), float(alpha), float(ln_eps)
+        return m, (emb, pe, heads_w, mix, layers, tensors)     # (the second item keeps what m points to alive)
+
+    def forward(self, query, doc, params, heads, numlayers, usemask, alpha, pad, ln_eps=1e-5, mixer=None, features=False, check=True):
+        """int64 query ids [B, Q], document ids [B, L] -> fp32 scores [B] (and the [B, 22] features s_log_k | s_len_k with features=True)"""
+        _need_gpu(query, doc)
+        q, d = _i64(query), _i64(doc)
+        B, Q = q.shape
+        L = d.shape[1]
+        if d.shape[0] != B:
+            raise ValueError(f"{B} query rows for {d.shape[0]} documents")
+        m, keep = self.model(params, heads, numlayers, usemask, alpha, pad, ln_eps, mixer)
+        lib = _lib.load()
+        one = lib.capamd_tk_workspace_bytes(ctypes.byref(m), 1, Q, L)
+        if one < 0:
+            raise ValueError(f"unsupported TK geometry: dim {m.dim}, heads {m.heads}, ffdim {m.ffdim}, layers {m.numlayers}, Q {Q}, L {L} "
+                             f"(dim <= 512, dim % heads == 0, dim / heads <= 64, ffdim <= 512, layers >= 1, Q <= 32, L <= {m.max_len})")
+        nb = self.docs_per_microbatch
+        if nb is None:
+            per_doc = max(1, lib.capamd_tk_workspace_bytes(ctypes.byref(m), 2, Q, L) - one)
+            nb = max(1, TK_WORKSPACE_BUDGET // per_doc)
+        nb = max(1, min(int(nb), max(B, 1)))
+        need = lib.capamd_tk_workspace_bytes(ctypes.byref(m), nb, Q, L)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != q.device:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        out = torch.empty(B, dtype=torch.float32, device=q.device)
+        feats = torch.empty((B, 22), dtype=torch.float32, device=q.device) if features else None
+        st = status_word(q.device)
+        rc = lib.capamd_tk_forward(_ptr(q), _ptr(d), B, Q, L, ctypes.byref(m), nb, _ptr(self._ws), self._ws.numel(), _ptr(out), _ptr(feats),
+                                   _ptr(st.t), _stream())
+        _lib.check(rc, "capamd_tk_forward")
+        if check:
+            st.raise_if_set()
+        return (out, feats) if features else out

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CAPAMD_VERSION 401
+#define CAPAMD_VERSION 402
 
 #define CAPAMD_OK 0
 #define CAPAMD_ERR_ARG 1       /* null pointer / bad size / unsupported configuration */
@@ -397,6 +397,42 @@ int capamd_parade_passage_cls(const int64_t* ids, const int64_t* mask, const int
                               void* stream);
 int capamd_parade_head(const float* cls_rows, int B, int P, const capamd_parade_head_model* hm, void* workspace, int64_t workspace_bytes,
                        float* out, float* aggregated_out, void* stream);
+
+/* ---- TK (reference capreolus/reranker/TK.py, TK_class.forward :124-143, called from TK.test) ------------------------------------
+ * score[b] of query ids q_ids [B, Q] against document ids d_ids [B, L] (int64), fp32 throughout:
+ *   x = emb[id] + pe[position]; numlayers post-norm TransformerEncoderLayers (ReLU, LayerNorm eps ln_eps, no dropout), the query and
+ *   the document encoded as separate sequences; usemask != 0: a position whose embedding row is all zeros is excluded as query and as
+ *   key of the attention of its own sequence (a row that attends to nothing gets a zero attention output);
+ *   e = a emb[id] + (1 - a) x_final with a = *mixer (mixer != NULL) or alpha; cosine of every (query, document) position pair, 0 where
+ *   either id equals `pad`; the 11 kernels exp(-(c - mu)^2) / (2 sigma^2) (mu = -0.9, -0.7, .., 0.9, 1.0, sigma = 0.1) summed over
+ *   all L positions; s_log_k = sum_q log2(.), s_len_k = sum_q (.) / L; score = comb_w . [s_log_w . s_log_k, s_len_w . s_len_k].
+ *   features_out (optional) [B][22] = s_log_k, s_len_k.
+ * Weights in the padded layout (built once per set of weights by the caller; every pad element 0, tensors 16-byte aligned):
+ *   Dp = roundup(dim, 64), hd = dim / heads, hs = roundup(hd, 16), Hs = roundup(heads * hs, 64), Fp = roundup(ffdim, 64);
+ *   wqkv [3 Hs][Dp]: row p Hs + h hs + j (p = q, k, v; j < hd) = in_proj_weight row p dim + h hd + j;  bqkv [3 Hs] likewise;
+ *   wo [Dp][Hs]: column h hs + j = out_proj.weight column h hd + j;  bo, ln1_*, ln2_*, b2 [Dp];  w1 [Fp][Dp], b1 [Fp];  w2 [Dp][Fp].
+ * emb [vocab][dim] and pe [max_len][dim] (position_encoder.pe) are read in place; ids outside [0, vocab) are scored as a zero row and
+ * set CAPAMD_STATUS_DOC_ID_RANGE / _QUERY_ID_RANGE (nn.Embedding raises).  Limits: dim <= 512, dim % heads == 0, hd <= 64,
+ * ffdim <= 512, numlayers >= 1, 1 <= Q <= 32, 1 <= L <= max_len.  Documents run in micro-batches of docs_per_microbatch; the
+ * workspace (256-byte aligned) is capamd_tk_workspace_bytes(m, docs_per_microbatch, Q, L) bytes (-1: unsupported geometry).  Each
+ * document's score is independent of the micro-batch size and of the other documents of the call, bit for bit. */
+typedef struct capamd_tk_layer {
+  const float *wqkv, *bqkv, *wo, *bo, *ln1_g, *ln1_b, *w1, *b1, *w2, *b2, *ln2_g, *ln2_b;
+} capamd_tk_layer;
+typedef struct capamd_tk_model {
+  const float* emb;                      /* [vocab][dim]    embedding.weight */
+  const float* pe;                       /* [max_len][dim]  position_encoder.pe */
+  const capamd_tk_layer* layers_host;    /* [numlayers], a HOST array of device pointers */
+  const float* mixer;                    /* [1] the mixer parameter (usemixer), or NULL: alpha */
+  const float *s_log_w, *s_len_w, *comb_w;   /* [11], [11], [2] */
+  int64_t vocab, pad;
+  int dim, heads, ffdim, numlayers, max_len, usemask;
+  float alpha, ln_eps;
+} capamd_tk_model;
+
+int64_t capamd_tk_workspace_bytes(const capamd_tk_model* m, int docs_per_microbatch, int Q, int L);
+int capamd_tk_forward(const int64_t* q_ids, const int64_t* d_ids, int B, int Q, int L, const capamd_tk_model* m, int docs_per_microbatch,
+                      void* workspace, int64_t workspace_bytes, float* out, float* features_out, int* status, void* stream);
 
 /* ---- ConvKNRM ------------------------------------------------------------------------
  * Replaces ConvKNRM_class.forward, capreolus/reranker/ConvKNRM.py:42-77 (called from ConvKNRM.test :112-116).
