@@ -331,6 +331,12 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv
   for (int c = 0; c < NC; ++c)
 #pragma unroll
     for (int r = 0; r < 4; ++r) dst[16 * c + 4 * g + r] = live ? o[c][r] * inv : 0.f;
+  // the pad columns past the last head slot (Hs = heads HS rounded up to 64; fewer than 64, a multiple of 16): the out-proj GEMM reads
+  // them against zero weights, so they must be 0 and not whatever the workspace held (0 x NaN = NaN)
+  if (h == (int)gridDim.y - 1)
+    for (int c = (h + 1) * HS + 4 * g; c < Hs; c += 16)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ctx[(base + q) * (int64_t)Hs + c + r] = 0.f;
 }
 
 // One document per workgroup: e_j = a emb[d_j] + (1 - a) xd_j (likewise the query rows, into LDS 8 at a time), cos[i][j] =

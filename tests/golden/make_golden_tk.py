@@ -3,7 +3,7 @@ numpy-seeded embeddings, weights and ids of tests/tk_case.py.  Records per pair 
 s_log_fcc / s_len_fcc, taken with forward hooks), the state_dict names and shapes, and for tk_grad the gradients of a fixed loss in
 training mode with dropout p = 0.  Build container only; data out, no code.
 
-    python tests/golden/make_golden_tk.py            (from the repository root)
+    python tests/golden/make_golden_tk.py [CASE ...]     (from the repository root; no names: every case of tk_case.CASES)
 
 usemask: the reference tiles its mask head-major while nn.MultiheadAttention's rows are batch-major, so in a batch of documents with
 different masks a head reads another document's mask.  Masked cases are therefore recorded one document per call (the semantics the
@@ -84,7 +84,11 @@ def main():
 
     load_reference()
     TK = importlib.import_module("capreolus.reranker.TK")
-    for name in tk_case.CASES:
+    names = sys.argv[1:] or list(tk_case.CASES)
+    unknown = [n for n in names if n not in tk_case.CASES]
+    if unknown:
+        raise SystemExit(f"unknown case(s) {unknown}; known: {list(tk_case.CASES)}")
+    for name in names:
         gen(name, TK)
 
 

@@ -41,6 +41,22 @@ def test_state_dict_names_and_shapes_match_the_reference(name):
     np.testing.assert_array_equal(m.position_encoder.pe[:16, 0].numpy(), c["pe_head"])
 
 
+@pytest.mark.parametrize("name", list(tk_case.CASES))
+def test_fixture_ids_are_what_tk_case_draws(name):
+    """the fixtures' recorded ids are tk_case.inputs' (so its per-case options left the older cases' streams alone), with the edge
+    patterns the kernels' tests rely on"""
+    c = tk_case.load(name)
+    q, d = tk_case.inputs(name)
+    np.testing.assert_array_equal(c["query"], q)
+    np.testing.assert_array_equal(c["posdoc"], d)
+    assert (d == 0).any() and (q == 0).any() and (d == tk_case.ZERO_TOKEN).any() and (q == tk_case.ZERO_TOKEN).any()
+    if tk_case.CASES[name].get("dead_tiles"):
+        Z = tk_case.ZERO_TOKEN
+        assert (d[4, :130] == Z).all() and d[4, 130] != Z and (d[5] == Z).all()
+        assert (d[6] != Z).sum() == 1 and (d[6] != Z).argmax() > 128
+        assert np.isin(q[6], (0, Z)).all()
+
+
 def test_save_and_load_weights_round_trip(tmp_path):
     r, m = _model("tk_small")
     opt = torch.optim.Adam([p for p in m.parameters() if p.requires_grad], lr=1e-3)
