@@ -16,30 +16,17 @@
 //   convknrm_gather_kernel    the pooling backward's per-(view, chunk) partial d a_q summed in their order into d qrep; its per-block
 //                             d mu / d sigma partials summed in order, Adam on the kernel parameters
 //   convknrm_adam_kernel      Adam over the convolution weights and biases from the gradients ngram_conv's backward wrote
-// Adam as torch.optim.Adam's non-capturable single-tensor path (torch/optim/adam.py): exp_avg.lerp_(g, 1 - beta1);
-// exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2); denom = sqrt(exp_avg_sq) / sqrt(bias_correction2) + eps;
-// param.addcdiv_(exp_avg, denom, value = -lr / bias_correction1) - the step scalars come from the host, computed in double.
+// The pairwise loss and Adam's update are train_step.h's (shared by every fused training step).
 #include "capreolus_amd.h"
+#include "train_step.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+using namespace capamd;
 
 namespace {
 
 constexpr int kCkMaxK = 16, kCkMaxG = 4, kCkMaxBatch = 512, kCkMaxFeat = kCkMaxK * kCkMaxG * kCkMaxG;
-
-struct AdamScalars {
-  float step_size, one_minus_beta1, beta2, eps, bc2_sqrt;
-};
-
-__device__ __forceinline__ void adam_update(float* p, float* m, float* v, float g, const AdamScalars& s) {
-  float mm = *m, vv = *v;
-  mm = mm + (g - mm) * s.one_minus_beta1;
-  vv = vv * s.beta2 + (1.f - s.beta2) * (g * g);
-  *m = mm;
-  *v = vv;
-  const float denom = sqrtf(vv) / s.bc2_sqrt + s.eps;
-  *p = *p - s.step_size * (mm / denom);
-}
 
 // parameter slots of the pointer table (each slot: parameter, exp_avg, exp_avg_sq; a null exp_avg = not trained)
 struct ParamTable {
@@ -88,19 +75,8 @@ __global__ __launch_bounds__(256) void convknrm_tail_kernel(TailArgs a) {
       }
       sc[h] = v;
     }
-    float li, gp, gn;      // loss of the pair, d loss / d score of its positive / negative document
-    if (a.loss_type == 0) {
-      const float mrg = 1.f - (sc[0] - sc[1]);
-      li = fmaxf(mrg, 0.f);
-      const float on = mrg >= 0.f ? inv_b : 0.f;      // (torch.clamp's backward passes the gradient at the boundary)
-      gp = -on;
-      gn = on;
-    } else {
-      const float mx = fmaxf(sc[0], sc[1]), e0 = expf(sc[0] - mx), e1 = expf(sc[1] - mx), p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-      li = 1.f - p0;
-      gp = -p0 * p1 * inv_b;
-      gn = p0 * p1 * inv_b;
-    }
+    float gp, gn;      // d loss / d score of the positive / negative document
+    const float li = pair_loss(sc[0], sc[1], a.loss_type, inv_b, gp, gn);
     gsc[0][i] = gp * dt[0];
     gsc[1][i] = gn * dt[1];
     lsum[i] = li;
@@ -114,9 +90,7 @@ __global__ __launch_bounds__(256) void convknrm_tail_kernel(TailArgs a) {
   // one thread per element of the Linear (and one for the loss): its gradient summed over the batch in pair order, then Adam
   for (int j = tid; j < NF + 2; j += 256) {
     if (j == NF + 1) {
-      float l = 0.f;
-      for (int i = 0; i < a.B; ++i) l += lsum[i];
-      a.loss_out[0] = l * inv_b;
+      write_mean_loss(lsum, a.B, inv_b, a.loss_out);
       continue;
     }
     float g = 0.f;
@@ -236,7 +210,7 @@ extern "C" int capamd_convknrm_train_step(const int64_t* q_ids, const int64_t* d
                                           float one_minus_beta1, float beta2, float eps, float bc2_sqrt, float* loss_out, float* workspace,
                                           size_t workspace_floats, int* status, void* stream) {
   if (!q_ids || !d_ids || !emb || !ptrs || !loss_out || !workspace || !status) return CAPAMD_ERR_ARG;
-  if (B < 1 || B > kCkMaxBatch || G < 1 || G > kCkMaxG || K < 1 || K > kCkMaxK || loss_type < 0 || loss_type > 1 || !(bc2_sqrt > 0.f)) return CAPAMD_ERR_ARG;
+  if (B < 1 || B > kCkMaxBatch || G < 1 || G > kCkMaxG || K < 1 || K > kCkMaxK || !train_step_scalars_ok(loss_type, bc2_sqrt)) return CAPAMD_ERR_ARG;
   if (reinterpret_cast<uintptr_t>(workspace) & 15) return CAPAMD_ERR_ALIGN;
   const StepLayout o = step_layout(B, Q, L, D, G, F, K, crossmatch);
   if (workspace_floats < o.total) return CAPAMD_ERR_WORKSPACE;

@@ -15,6 +15,7 @@
 //     are skipped; OOV document terms (id < 0) have sim exactly 0 -> added to bin(0) in closed form.
 #include "capreolus_amd.h"
 #include "interaction.h"
+#include "train_step.h"
 #include "interaction_stream.h"
 #include <stdlib.h>
 
@@ -464,7 +465,7 @@ struct DrmmStepArgs {
   int B, Q, NB, nodes;
   float* const* ptrs;
   int loss_type;
-  float step_size, one_minus_beta1, beta2, eps, bc2_sqrt;
+  AdamScalars adam;
   float* loss_out;
   float* inter;           // workspace [B][Q]: d loss / d gate logit
 };
@@ -514,18 +515,8 @@ __global__ __launch_bounds__(256) void drmm_step_kernel(DrmmStepArgs a) {
       sagg[h] = acc;
       score[h] = __builtin_fmaf(wo, acc, bo);
     }
-    float li, ds[2];
-    if (a.loss_type == 0) {
-      const float mrg = 1.f - (score[0] - score[1]);
-      li = fmaxf(mrg, 0.f);
-      const float on = mrg >= 0.f ? inv_b : 0.f;
-      ds[0] = -on; ds[1] = on;
-    } else {
-      const float m2 = fmaxf(score[0], score[1]), e0 = expf(score[0] - m2), e1 = expf(score[1] - m2), p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-      li = 1.f - p0;
-      ds[0] = -p0 * p1 * inv_b; ds[1] = p0 * p1 * inv_b;
-    }
-    lsum[i] = li;
+    float ds[2];
+    lsum[i] = pair_loss(score[0], score[1], a.loss_type, inv_b, ds[0], ds[1]);
     dso[i] = ds[0] * sagg[0] + ds[1] * sagg[1];       // d loss / d output_layer.weight of this pair
     dbo[i] = ds[0] + ds[1];
     float dg[kMaxQ];
@@ -547,9 +538,7 @@ __global__ __launch_bounds__(256) void drmm_step_kernel(DrmmStepArgs a) {
   const int n_el = N * NB + N + N + 4;
   for (int j = tid; j <= n_el; j += 256) {          // B
     if (j == n_el) {
-      float l = 0.f;
-      for (int i = 0; i < a.B; ++i) l += lsum[i];
-      a.loss_out[0] = l * inv_b;
+      write_mean_loss(lsum, a.B, inv_b, a.loss_out);
       continue;
     }
     float gsum = 0.f;
@@ -579,16 +568,7 @@ __global__ __launch_bounds__(256) void drmm_step_kernel(DrmmStepArgs a) {
         for (int i = 0; i < a.B; ++i) gsum += dbo[i];
       }
     }
-    float* pp = a.ptrs[slot] + el;
-    float* pm = a.ptrs[7 + slot] + el;
-    float* pv = a.ptrs[14 + slot] + el;
-    float m = *pm, v = *pv;
-    m = m + (gsum - m) * a.one_minus_beta1;                    // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * a.beta2 + (1.f - a.beta2) * (gsum * gsum);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-    *pm = m;
-    *pv = v;
-    const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-    *pp = *pp - a.step_size * (m / denom);                     // param.addcdiv_(exp_avg, denom, value = -lr / bias_correction1)
+    adam_update(a.ptrs[slot] + el, a.ptrs[7 + slot] + el, a.ptrs[14 + slot] + el, gsum, a.adam);
   }
 }
 
@@ -603,7 +583,7 @@ extern "C" int capamd_drmm_train_step(const int64_t* q_ids, const int64_t* pos_i
   if (!q_ids || !pos_ids || !neg_ids || !idf || !packed || !edges || !ptrs || !loss_out || !workspace || !status) return CAPAMD_ERR_ARG;
   if (B < 1 || B > kMaxStepBatch || Q < 1 || Q > kMaxQ || L < 1 || L > 32768 || V < 1 || V > 0x7fffffffLL) return CAPAMD_ERR_ARG;
   if (nbins < 1 || nbins + 1 > kMaxBins || hist_type < 0 || hist_type > 2 || nodes < 1 || nodes > kMaxStepNodes || capamd_packed_row_stride(D) < 0) return CAPAMD_ERR_ARG;
-  if (loss_type < 0 || loss_type > 1 || !(bc2_sqrt > 0.f) || 2 * B * Q > kMaxStepDQ) return CAPAMD_ERR_ARG;
+  if (!train_step_scalars_ok(loss_type, bc2_sqrt) || 2 * B * Q > kMaxStepDQ) return CAPAMD_ERR_ARG;
   if (workspace_floats < capamd_drmm_train_step_workspace_floats(B, Q, nbins, nodes)) return CAPAMD_ERR_WORKSPACE;
   const int NB = nbins + 1;
   float* feat = workspace;
@@ -613,7 +593,7 @@ extern "C" int capamd_drmm_train_step(const int64_t* q_ids, const int64_t* pos_i
               nullptr, nullptr, nullptr, nullptr, status, feat, neg_ids, B};
   const int rc = drmm_features_launch(fa, stream);
   if (rc != CAPAMD_OK) return rc;
-  DrmmStepArgs a{feat, q_ids, idf, B, Q, NB, nodes, ptrs, loss_type, step_size, one_minus_beta1, beta2, eps, bc2_sqrt, loss_out, inter};
+  DrmmStepArgs a{feat, q_ids, idf, B, Q, NB, nodes, ptrs, loss_type, {step_size, one_minus_beta1, beta2, eps, bc2_sqrt}, loss_out, inter};
   hipLaunchKernelGGL(drmm_step_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
 }

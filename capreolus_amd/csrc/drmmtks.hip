@@ -11,6 +11,7 @@
 // gathered: n1 ones (OOV exact matches) and n0 zeros (pads and other OOV terms).
 #include "capreolus_amd.h"
 #include "interaction.h"
+#include "train_step.h"
 
 using namespace capamd;
 
@@ -254,7 +255,7 @@ struct TksStepArgs {
   int B, Q, topk;
   float* const* ptrs;
   int loss_type;
-  float step_size, one_minus_beta1, beta2, eps, bc2_sqrt;
+  AdamScalars adam;
   float* loss_out;
   float* grads;           // [B][topk + 4] per-pair gradient contributions (workspace)
 };
@@ -289,18 +290,8 @@ __global__ __launch_bounds__(256) void drmmtks_step_kernel(TksStepArgs a) {
       sagg[h] = acc;
       score[h] = __builtin_fmaf(wo, acc, bo);
     }
-    float li, ds[2];
-    if (a.loss_type == 0) {
-      const float mrg = 1.f - (score[0] - score[1]);
-      li = fmaxf(mrg, 0.f);
-      const float on = mrg >= 0.f ? inv_b : 0.f;
-      ds[0] = -on; ds[1] = on;
-    } else {
-      const float m2 = fmaxf(score[0], score[1]), e0 = expf(score[0] - m2), e1 = expf(score[1] - m2), p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-      li = 1.f - p0;
-      ds[0] = -p0 * p1 * inv_b; ds[1] = p0 * p1 * inv_b;
-    }
-    lsum[i] = li;
+    float ds[2];
+    lsum[i] = pair_loss(score[0], score[1], a.loss_type, inv_b, ds[0], ds[1]);
     // backward: this pair's contribution to every parameter element
     float* G = a.grads + (int64_t)i * NP;
     float dwf[kMaxTopK], dbf = 0.f, dwg = 0.f, dwo = 0.f, dbo = 0.f;
@@ -328,24 +319,13 @@ __global__ __launch_bounds__(256) void drmmtks_step_kernel(TksStepArgs a) {
   const int j = tid;
   if (j > NP) return;
   if (j == NP) {
-    float l = 0.f;
-    for (int i = 0; i < a.B; ++i) l += lsum[i];
-    a.loss_out[0] = l * inv_b;
+    write_mean_loss(lsum, a.B, inv_b, a.loss_out);
     return;
   }
   float gsum = 0.f;
   for (int i = 0; i < a.B; ++i) gsum += a.grads[(int64_t)i * NP + j];
   const int slot = j < K ? 0 : j - K + 1, el = j < K ? j : 0;
-  float* pp = a.ptrs[slot] + el;
-  float* pm = a.ptrs[5 + slot] + el;
-  float* pv = a.ptrs[10 + slot] + el;
-  float m = *pm, v = *pv;
-  m = m + (gsum - m) * a.one_minus_beta1;                    // exp_avg.lerp_(grad, 1 - beta1)
-  v = v * a.beta2 + (1.f - a.beta2) * (gsum * gsum);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-  *pm = m;
-  *pv = v;
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  *pp = *pp - a.step_size * (m / denom);                     // param.addcdiv_(exp_avg, denom, value = -lr / bias_correction1)
+  adam_update(a.ptrs[slot] + el, a.ptrs[5 + slot] + el, a.ptrs[10 + slot] + el, gsum, a.adam);
 }
 
 extern "C" size_t capamd_drmmtks_train_step_workspace_floats(int B, int Q, int topk) {
@@ -358,7 +338,7 @@ extern "C" int capamd_drmmtks_train_step(const int64_t* q_ids, const int64_t* po
                                          size_t workspace_floats, int* status, void* stream) {
   if (!q_ids || !pos_ids || !neg_ids || !idf || !packed || !ptrs || !loss_out || !workspace || !status) return CAPAMD_ERR_ARG;
   if (B < 1 || B > kMaxStepBatch || Q < 1 || Q > kMaxQ || L < 1 || L > 32768 || V < 1 || V > 0x7fffffffLL) return CAPAMD_ERR_ARG;
-  if (topk < 1 || topk > kMaxTopK || topk > L || capamd_packed_row_stride(D) < 0 || loss_type < 0 || loss_type > 1 || !(bc2_sqrt > 0.f)) return CAPAMD_ERR_ARG;
+  if (topk < 1 || topk > kMaxTopK || topk > L || capamd_packed_row_stride(D) < 0 || !train_step_scalars_ok(loss_type, bc2_sqrt)) return CAPAMD_ERR_ARG;
   if (workspace_floats < capamd_drmmtks_train_step_workspace_floats(B, Q, topk)) return CAPAMD_ERR_WORKSPACE;
   float* feat = workspace;
   float* grads = workspace + (size_t)2 * B * Q * topk;
@@ -366,7 +346,7 @@ extern "C" int capamd_drmmtks_train_step(const int64_t* q_ids, const int64_t* po
   TksArgs fa{ids, nullptr, 2 * B, Q, L, packed, V, topk, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, status, feat, neg_ids, B};
   const int rc = drmmtks_features_launch(fa, D, stream);
   if (rc != CAPAMD_OK) return rc;
-  TksStepArgs a{feat, q_ids, idf, B, Q, topk, ptrs, loss_type, step_size, one_minus_beta1, beta2, eps, bc2_sqrt, loss_out, grads};
+  TksStepArgs a{feat, q_ids, idf, B, Q, topk, ptrs, loss_type, {step_size, one_minus_beta1, beta2, eps, bc2_sqrt}, loss_out, grads};
   hipLaunchKernelGGL(drmmtks_step_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
 }

@@ -25,6 +25,7 @@
 #include "capreolus_amd.h"
 #include "interaction.h"
 #include "interaction_stream.h"
+#include "train_step.h"
 #include <stdlib.h>
 
 using namespace capamd;
@@ -573,7 +574,7 @@ struct KnrmStepArgs {
   int B, K;
   float* const* ptrs;
   int train_kernels, scoretanh, loss_type;
-  float step_size, one_minus_beta1, beta2, eps, bc2_sqrt;
+  AdamScalars adam;
   float* loss_out;
 };
 
@@ -597,19 +598,8 @@ __global__ __launch_bounds__(256) void knrm_step_kernel(KnrmStepArgs a) {
       }
       sc[h] = v;
     }
-    float li, gp, gn;      // loss of the pair, d loss / d score of its positive / negative document
-    if (a.loss_type == 0) {
-      const float mrg = 1.f - (sc[0] - sc[1]);
-      li = fmaxf(mrg, 0.f);
-      const float on = mrg >= 0.f ? inv_b : 0.f;      // (torch.clamp's backward passes the gradient at the boundary)
-      gp = -on;
-      gn = on;
-    } else {
-      const float mx = fmaxf(sc[0], sc[1]), e0 = expf(sc[0] - mx), e1 = expf(sc[1] - mx), p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-      li = 1.f - p0;
-      gp = -p0 * p1 * inv_b;
-      gn = p0 * p1 * inv_b;
-    }
+    float gp, gn;      // d loss / d score of the positive / negative document
+    const float li = pair_loss(sc[0], sc[1], a.loss_type, inv_b, gp, gn);
     gsc[0][i] = gp * dt[0];
     gsc[1][i] = gn * dt[1];
     lsum[i] = li;
@@ -619,9 +609,7 @@ __global__ __launch_bounds__(256) void knrm_step_kernel(KnrmStepArgs a) {
   const int j = tid;
   if (j > 3 * K + 1) return;
   if (j == 3 * K + 1) {
-    float l = 0.f;
-    for (int i = 0; i < a.B; ++i) l += lsum[i];
-    a.loss_out[0] = l * inv_b;
+    write_mean_loss(lsum, a.B, inv_b, a.loss_out);
     return;
   }
   if (j < 2 * K && !a.train_kernels) return;
@@ -638,16 +626,7 @@ __global__ __launch_bounds__(256) void knrm_step_kernel(KnrmStepArgs a) {
     for (int i = 0; i < a.B; ++i) g += gsc[0][i] + gsc[1][i];
   }
   const int slot = j < 2 * K ? j : (j < 3 * K ? 2 * K : 2 * K + 1), el = (j >= 2 * K && j < 3 * K) ? j - 2 * K : 0;
-  float* pp = a.ptrs[slot] + el;
-  float* pm = a.ptrs[P + slot] + el;
-  float* pv = a.ptrs[2 * P + slot] + el;
-  float m = *pm, v = *pv;
-  m = m + (g - m) * a.one_minus_beta1;                       // exp_avg.lerp_(grad, 1 - beta1)
-  v = v * a.beta2 + (1.f - a.beta2) * (g * g);               // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-  *pm = m;
-  *pv = v;
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  *pp = *pp - a.step_size * (m / denom);                     // param.addcdiv_(exp_avg, denom, value = -lr / bias_correction1)
+  adam_update(a.ptrs[slot] + el, a.ptrs[P + slot] + el, a.ptrs[2 * P + slot] + el, g, a.adam);
 }
 
 extern "C" size_t capamd_knrm_train_step_workspace_floats(int B, int K) { return B > 0 && K > 0 ? (size_t)6 * B * K : 0; }
@@ -658,7 +637,7 @@ extern "C" int capamd_knrm_train_step(const int64_t* q_ids, const int64_t* pos_i
                                       size_t workspace_floats, int* status, void* stream) {
   if (!q_ids || !pos_ids || !neg_ids || !packed || !ptrs || !loss_out || !workspace || !status) return CAPAMD_ERR_ARG;
   if (B < 1 || B > kMaxStepBatch || Q < 1 || L < 1 || L > 32768 || V < 1 || V > 0x7fffffffLL || K < 1 || K > kMaxK) return CAPAMD_ERR_ARG;
-  if (loss_type < 0 || loss_type > 1 || !(bc2_sqrt > 0.f) || capamd_packed_row_stride(D) < 0) return CAPAMD_ERR_ARG;
+  if (!train_step_scalars_ok(loss_type, bc2_sqrt) || capamd_packed_row_stride(D) < 0) return CAPAMD_ERR_ARG;
   if (workspace_floats < capamd_knrm_train_step_workspace_floats(B, K)) return CAPAMD_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)B * K;
@@ -667,8 +646,8 @@ extern "C" int capamd_knrm_train_step(const int64_t* q_ids, const int64_t* pos_i
   KnrmArgs fa{ids, 2 * B, Q, L, packed, V, nullptr, nullptr, K, nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, status, feat, dmu, dsg, ptrs, neg_ids, B};
   const int rc = knrm_features_launch(fa, D, stream);
   if (rc != CAPAMD_OK) return rc;
-  KnrmStepArgs a{{feat, feat + n}, {dmu, dmu + n}, {dsg, dsg + n}, B, K, ptrs, train_kernels, scoretanh, loss_type, step_size,
-                 one_minus_beta1, beta2, eps, bc2_sqrt, loss_out};
+  KnrmStepArgs a{{feat, feat + n}, {dmu, dmu + n}, {dsg, dsg + n}, B, K, ptrs, train_kernels, scoretanh, loss_type,
+                 {step_size, one_minus_beta1, beta2, eps, bc2_sqrt}, loss_out};
   hipLaunchKernelGGL(knrm_step_kernel, dim3(1), dim3(256), 0, s, a);
   return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
 }

@@ -15,8 +15,11 @@
 // Backward: one workgroup per (n-gram size, filter): its threads share the (pair, q, rank) entries, every thread sums its entries in
 // order, the threads' partial sums are added in a fixed tree: deterministic, no atomics.
 #include "capreolus_amd.h"
+#include "train_step.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+using namespace capamd;
 
 namespace {
 
@@ -198,19 +201,6 @@ namespace {
 
 constexpr int kStepMaxNg = kTrMaxNg, kStepMaxH = 128, kStepMaxX = kTrMaxQ * (kTrMaxNg * kTrMaxK + 1), kStepLdsFloats = 36 * 1024;
 
-struct StepAdam {
-  float step_size, one_minus_beta1, beta2, eps, bc2_sqrt;
-};
-
-__device__ __forceinline__ void step_adam(float* p, float* m, float* v, float g, const StepAdam& s) {
-  float mm = *m, vv = *v;      // torch.optim.Adam, single-tensor path: lerp_, mul_ / addcmul_, sqrt / bias_correction2_sqrt + eps, addcdiv_
-  mm = mm + (g - mm) * s.one_minus_beta1;
-  vv = vv * s.beta2 + (1.f - s.beta2) * (g * g);
-  *m = mm;
-  *v = vv;
-  *p = *p - s.step_size * (mm / (sqrtf(vv) / s.bc2_sqrt + s.eps));
-}
-
 struct ConvParams {
   float *w[kStepMaxNg], *wm[kStepMaxNg], *wv[kStepMaxNg];      // ngrams.{i}.conv.weight [nf, 1, ng, ng] and its moments
   float *b[kStepMaxNg], *bm[kStepMaxNg], *bv[kStepMaxNg];      // ngrams.{i}.conv.bias [nf]
@@ -219,7 +209,7 @@ struct ConvParams {
 
 // mode 0: parameters -> conv_w / conv_b (the layout of the convmax kernels); mode 1: Adam from dw / db in that layout
 __global__ __launch_bounds__(256) void pacrr_conv_params_kernel(ConvParams c, float* conv_w, float* conv_b, const float* dw, const float* db, int mode,
-                                                                StepAdam adam) {
+                                                                AdamScalars adam) {
   const int gi = blockIdx.y, ng = c.mingram + gi, nw = c.nf * ng * ng;
   const int off = w_offset(c.mingram, ng, c.nf);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < nw + c.nf; i += gridDim.x * 256) {
@@ -229,9 +219,9 @@ __global__ __launch_bounds__(256) void pacrr_conv_params_kernel(ConvParams c, fl
       if (isw) conv_w[off + e] = c.w[gi][e];
       else conv_b[gi * c.nf + e] = c.b[gi][e];
     } else if (isw) {
-      if (c.wm[gi]) step_adam(c.w[gi] + e, c.wm[gi] + e, c.wv[gi] + e, dw[off + e], adam);
+      if (c.wm[gi]) adam_update(c.w[gi] + e, c.wm[gi] + e, c.wv[gi] + e, dw[off + e], adam);
     } else if (c.bm[gi]) {
-      step_adam(c.b[gi] + e, c.bm[gi] + e, c.bv[gi] + e, db[gi * c.nf + e], adam);
+      adam_update(c.b[gi] + e, c.bm[gi] + e, c.bv[gi] + e, db[gi * c.nf + e], adam);
     }
   }
 }
@@ -243,7 +233,7 @@ struct MlpArgs {
   float *w1, *w1m, *w1v, *b1, *b1m, *b1v;      // linear1 [H][X], X = Q (nt + use_idf)
   float *w2, *w2m, *w2v, *b2, *b2m, *b2v;      // linear2 [H][H]
   float *w3, *w3m, *w3v, *b3, *b3m, *b3v;      // linear3 [1][H]
-  StepAdam adam;
+  AdamScalars adam;
   float* gtop;          // [N, Q, nt]
   float* loss_out;
 };
@@ -305,19 +295,8 @@ __global__ __launch_bounds__(256) void pacrr_mlp_step_kernel(MlpArgs a) {
   const float inv_b = 1.f / (float)a.B;
   for (int i = tid; i < a.B; i += 256) {
     const float sp = sc[i], sn = sc[a.B + i];
-    float li, gp, gn;
-    if (a.loss_type == 0) {
-      const float mrg = 1.f - (sp - sn);
-      li = fmaxf(mrg, 0.f);
-      const float on = mrg >= 0.f ? inv_b : 0.f;      // (torch.clamp's backward passes the gradient at the boundary)
-      gp = -on;
-      gn = on;
-    } else {
-      const float mx = fmaxf(sp, sn), e0 = expf(sp - mx), e1 = expf(sn - mx), p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-      li = 1.f - p0;
-      gp = -p0 * p1 * inv_b;
-      gn = p0 * p1 * inv_b;
-    }
+    float gp, gn;
+    const float li = pair_loss(sp, sn, a.loss_type, inv_b, gp, gn);
     gs[i] = gp;
     gs[a.B + i] = gn;
     ls[i] = li;
@@ -346,9 +325,7 @@ __global__ __launch_bounds__(256) void pacrr_mlp_step_kernel(MlpArgs a) {
   const int n1 = H * X, n2 = H * H, total = n1 + H + n2 + H + H + 1;
   for (int j = tid; j <= total; j += 256) {
     if (j == total) {
-      float l = 0.f;
-      for (int i = 0; i < a.B; ++i) l += ls[i];
-      a.loss_out[0] = l * inv_b;
+      write_mean_loss(ls, a.B, inv_b, a.loss_out);
       continue;
     }
     float g = 0.f;
@@ -376,7 +353,7 @@ __global__ __launch_bounds__(256) void pacrr_mlp_step_kernel(MlpArgs a) {
       for (int i = 0; i < a.B; ++i) g += gs[i] + gs[a.B + i];      // (pair by pair: exactly zero under a pairwise loss, as the other models' step kernels)
       p = a.b3; m = a.b3m; v = a.b3v;
     }
-    if (m) step_adam(p + e, m + e, v + e, g, a.adam);
+    if (m) adam_update(p + e, m + e, v + e, g, a.adam);
   }
 }
 
@@ -415,8 +392,8 @@ extern "C" int capamd_pacrr_train_step(const int64_t* q_ids, const int64_t* d_id
                                        float bc2_sqrt, float* loss_out, float* workspace, size_t workspace_floats, int* status, void* stream) {
   if (!q_ids || !d_ids || !packed || !ptrs || !loss_out || !workspace || !status || (use_idf && !idf)) return CAPAMD_ERR_ARG;
   if (B < 1 || mingram < 1 || maxgram < mingram || maxgram > kTrMaxNg || kmax < 1 || kmax > kTrMaxK || Q < 1 || Q > kTrMaxQ || L < kmax || L > kTrMaxL ||
-      nfilters < 1 || nfilters > kTrMaxF || combine < 1 || combine > kStepMaxH || nonlinearity < 0 || nonlinearity > 2 || loss_type < 0 || loss_type > 1 ||
-      !(bc2_sqrt > 0.f))
+      nfilters < 1 || nfilters > kTrMaxF || combine < 1 || combine > kStepMaxH || nonlinearity < 0 || nonlinearity > 2 ||
+      !train_step_scalars_ok(loss_type, bc2_sqrt))
     return CAPAMD_ERR_ARG;
   const int n_ng = maxgram - mingram + 1, nt = n_ng * kmax, N = 2 * B, P = 2 * n_ng + 6;
   const size_t lds_floats = mlp_lds_floats(B, Q, nt, use_idf ? 1 : 0, combine);
@@ -432,7 +409,7 @@ extern "C" int capamd_pacrr_train_step(const int64_t* q_ids, const int64_t* d_id
     cp.w[g] = ptrs[2 * g]; cp.wm[g] = ptrs[P + 2 * g]; cp.wv[g] = ptrs[2 * P + 2 * g];
     cp.b[g] = ptrs[2 * g + 1]; cp.bm[g] = ptrs[P + 2 * g + 1]; cp.bv[g] = ptrs[2 * P + 2 * g + 1];
   }
-  const StepAdam adam{step_size, one_minus_beta1, beta2, eps, bc2_sqrt};
+  const AdamScalars adam{step_size, one_minus_beta1, beta2, eps, bc2_sqrt};
   hipStream_t s = (hipStream_t)stream;
   float* w = workspace;
   int32_t* pos = reinterpret_cast<int32_t*>(w + o.pos);

@@ -593,7 +593,7 @@ class AdamStep:
         self.optimizer, self.group, self.params = optimizer, g, list(params)
         in_opt = {id(p) for p in g["params"]}
         # every tensor the optimizer trains must be one the device step updates: a parameter added to a model later would otherwise
-        # silently never move under the fused step - the trainer falls back to the captured-graph route on this error
+        # silently never move under the fused step - on this error the trainer takes eager steps with the same optimizer
         missing = in_opt - {id(p) for p in self.params if p is not None}
         if missing:
             raise NotImplementedError(f"{len(missing)} optimizer parameter(s) are not covered by this reranker's device training step")
@@ -617,6 +617,14 @@ class AdamStep:
         self.key = tuple(ptrs[0] + ptrs[1] + ptrs[2])
         self.trained = [p for p in self.params if p is not None and id(p) in in_opt]
 
+    @classmethod
+    def cached(cls, owner, optimizer, params):
+        """The AdamStep `owner` (a model) keeps for `optimizer` - rebuilt when the optimizer, a parameter's storage or its moments changed."""
+        hit = owner.__dict__.get("_adam_step")
+        if hit is None or hit.optimizer is not optimizer or hit.key[: len(params)] != tuple(p.data_ptr() for p in params) or not hit.still_valid():
+            hit = owner.__dict__["_adam_step"] = cls(optimizer, params)
+        return hit
+
     def still_valid(self):
         st = self.optimizer.state
         return all(len(st[p]) and st[p]["exp_avg"].data_ptr() in self.key for p in self.trained)
@@ -636,25 +644,36 @@ class AdamStep:
 _step_workspaces = {}
 
 
+def _train_step(entry, lead, ws_floats, adam, softmax, device, check):
+    """The tail every capamd_*_train_step call shares: `lead` are the model's own leading arguments, then loss type, the Adam step's
+    scalars, loss, workspace and status.  After a successful call the trained parameters' version counters are bumped (an exact no-op
+    x * 1: the kernels wrote them behind autograd's back), so that weight-derived caches notice.  Returns the loss [1]."""
+    ws = _step_workspace(device, int(ws_floats))
+    loss = torch.empty(1, dtype=torch.float32, device=device)
+    st = status_word(device)
+    rc = getattr(_lib.load(), entry)(*lead, int(bool(softmax)), *adam.advance(), _ptr(loss), _ptr(ws), ws.numel(), _ptr(st.t), _stream())
+    _lib.check(rc, entry)
+    adam.commit()
+    if check:
+        st.raise_if_set()
+    with torch.no_grad():
+        torch._foreach_mul_(adam.trained, 1.0)
+    return loss
+
+
+def _host_table(adam):
+    """The parameter / moment pointers as a host array (the entries whose kernels read them from launch arguments)."""
+    return (ctypes.c_void_p * len(adam.key))(*[p or None for p in adam.key])
+
+
 def knrm_train_step(query, posdoc, negdoc, packed, V, D, K, adam, train_kernels, scoretanh, softmax, check=True):
     """capamd_knrm_train_step: score(pos), score(neg), the trainer's pairwise loss, backward, Adam - on the device; returns the loss [1]."""
     _need_gpu(query, posdoc, negdoc, packed)
     q, dp, dn = _i64(query), _i64(posdoc), _i64(negdoc)
     B, Q = q.shape
     L = dp.shape[1]
-    lib = _lib.load()
-    ws = _step_workspace(q.device, int(lib.capamd_knrm_train_step_workspace_floats(B, K)))
-    loss = torch.empty(1, dtype=torch.float32, device=q.device)
-    step_size, omb1, b2, eps, bc2s = adam.advance()
-    st = status_word(q.device)
-    rc = lib.capamd_knrm_train_step(_ptr(q), _ptr(dp), _ptr(dn), B, Q, L, _ptr(packed), V, D, K, _ptr(adam.table), int(bool(train_kernels)),
-                                    int(bool(scoretanh)), int(bool(softmax)), step_size, omb1, b2, eps, bc2s, _ptr(loss), _ptr(ws), ws.numel(),
-                                    _ptr(st.t), _stream())
-    _lib.check(rc, "capamd_knrm_train_step")
-    adam.commit()
-    if check:
-        st.raise_if_set()
-    return loss
+    lead = (_ptr(q), _ptr(dp), _ptr(dn), B, Q, L, _ptr(packed), V, D, K, _ptr(adam.table), int(bool(train_kernels)), int(bool(scoretanh)))
+    return _train_step("capamd_knrm_train_step", lead, _lib.load().capamd_knrm_train_step_workspace_floats(B, K), adam, softmax, q.device, check)
 
 
 def convknrm_train_step(query, posdoc, negdoc, emb, G, F, K, crossmatch, adam, scoretanh, softmax, check=True):
@@ -664,19 +683,9 @@ def convknrm_train_step(query, posdoc, negdoc, emb, G, F, K, crossmatch, adam, s
     B, Q = q.shape
     L = dp.shape[1]
     q2, d2 = torch.cat([q, q]), torch.cat([dp, dn])
-    lib = _lib.load()
-    ws = _step_workspace(q.device, int(lib.capamd_convknrm_train_step_workspace_floats(B, Q, L, e.shape[1], G, F, K, int(bool(crossmatch)))))
-    loss = torch.empty(1, dtype=torch.float32, device=q.device)
-    step_size, omb1, b2, eps, bc2s = adam.advance()
-    ptrs = (ctypes.c_void_p * len(adam.key))(*[p or None for p in adam.key])
-    st = status_word(q.device)
-    rc = lib.capamd_convknrm_train_step(_ptr(q2), _ptr(d2), B, Q, L, _ptr(e), e.shape[0], e.shape[1], G, F, K, int(bool(crossmatch)), ptrs, int(bool(scoretanh)),
-                                        int(bool(softmax)), step_size, omb1, b2, eps, bc2s, _ptr(loss), _ptr(ws), ws.numel(), _ptr(st.t), _stream())
-    _lib.check(rc, "capamd_convknrm_train_step")
-    adam.commit()
-    if check:
-        st.raise_if_set()
-    return loss
+    lead = (_ptr(q2), _ptr(d2), B, Q, L, _ptr(e), e.shape[0], e.shape[1], G, F, K, int(bool(crossmatch)), _host_table(adam), int(bool(scoretanh)))
+    ws_floats = _lib.load().capamd_convknrm_train_step_workspace_floats(B, Q, L, e.shape[1], G, F, K, int(bool(crossmatch)))
+    return _train_step("capamd_convknrm_train_step", lead, ws_floats, adam, softmax, q.device, check)
 
 
 def pacrr_train_step_fits(B, Q, n_ngrams, kmax, use_idf, combine):
@@ -692,20 +701,10 @@ def pacrr_train_step(query, posdoc, negdoc, idf, packed, V, D, mingram, maxgram,
     B, Q = q.shape
     L = dp.shape[1]
     q2, d2, idf2 = torch.cat([q, q]), torch.cat([dp, dn]), torch.cat([idf, idf])
-    lib = _lib.load()
-    ws = _step_workspace(q.device, int(lib.capamd_pacrr_train_step_workspace_floats(B, Q, L, int(mingram), int(maxgram), int(nfilters), int(kmax))))
-    loss = torch.empty(1, dtype=torch.float32, device=q.device)
-    step_size, omb1, b2, eps, bc2s = adam.advance()
-    ptrs = (ctypes.c_void_p * len(adam.key))(*[p or None for p in adam.key])
-    st = status_word(q.device)
-    rc = lib.capamd_pacrr_train_step(_ptr(q2), _ptr(d2), _ptr(idf2), B, Q, L, _ptr(packed), V, D, int(mingram), int(maxgram), int(nfilters), int(kmax),
-                                     int(bool(use_idf)), int(combine), NONLINEARITIES[nonlinearity], ptrs, int(bool(softmax)), step_size, omb1, b2, eps, bc2s,
-                                     _ptr(loss), _ptr(ws), ws.numel(), _ptr(st.t), _stream())
-    _lib.check(rc, "capamd_pacrr_train_step")
-    adam.commit()
-    if check:
-        st.raise_if_set()
-    return loss
+    lead = (_ptr(q2), _ptr(d2), _ptr(idf2), B, Q, L, _ptr(packed), V, D, int(mingram), int(maxgram), int(nfilters), int(kmax), int(bool(use_idf)),
+            int(combine), NONLINEARITIES[nonlinearity], _host_table(adam))
+    ws_floats = _lib.load().capamd_pacrr_train_step_workspace_floats(B, Q, L, int(mingram), int(maxgram), int(nfilters), int(kmax))
+    return _train_step("capamd_pacrr_train_step", lead, ws_floats, adam, softmax, q.device, check)
 
 
 def _step_workspace(device, n):
@@ -722,19 +721,10 @@ def drmm_train_step(query, posdoc, negdoc, idf, packed, V, D, edges, hist_type, 
     q, dp, dn, idf = _i64(query), _i64(posdoc), _i64(negdoc), _f32(idf)
     B, Q = q.shape
     L = dp.shape[1]
-    lib = _lib.load()
-    ws = _step_workspace(q.device, int(lib.capamd_drmm_train_step_workspace_floats(B, Q, edges.numel(), int(nodes))))
-    loss = torch.empty(1, dtype=torch.float32, device=q.device)
-    step_size, omb1, b2, eps, bc2s = adam.advance()
-    st = status_word(q.device)
-    rc = lib.capamd_drmm_train_step(_ptr(q), _ptr(dp), _ptr(dn), _ptr(idf), B, Q, L, _ptr(packed), V, D, _ptr(edges), edges.numel(), HIST_TYPES[hist_type],
-                                    int(nodes), _ptr(adam.table), int(bool(softmax)), step_size, omb1, b2, eps, bc2s, _ptr(loss), _ptr(ws), ws.numel(),
-                                    _ptr(st.t), _stream())
-    _lib.check(rc, "capamd_drmm_train_step")
-    adam.commit()
-    if check:
-        st.raise_if_set()
-    return loss
+    lead = (_ptr(q), _ptr(dp), _ptr(dn), _ptr(idf), B, Q, L, _ptr(packed), V, D, _ptr(edges), edges.numel(), HIST_TYPES[hist_type], int(nodes),
+            _ptr(adam.table))
+    ws_floats = _lib.load().capamd_drmm_train_step_workspace_floats(B, Q, edges.numel(), int(nodes))
+    return _train_step("capamd_drmm_train_step", lead, ws_floats, adam, softmax, q.device, check)
 
 
 def drmmtks_train_step(query, posdoc, negdoc, idf, packed, V, D, topk, adam, softmax, check=True):
@@ -743,18 +733,9 @@ def drmmtks_train_step(query, posdoc, negdoc, idf, packed, V, D, topk, adam, sof
     q, dp, dn, idf = _i64(query), _i64(posdoc), _i64(negdoc), _f32(idf)
     B, Q = q.shape
     L = dp.shape[1]
-    lib = _lib.load()
-    ws = _step_workspace(q.device, int(lib.capamd_drmmtks_train_step_workspace_floats(B, Q, int(topk))))
-    loss = torch.empty(1, dtype=torch.float32, device=q.device)
-    step_size, omb1, b2, eps, bc2s = adam.advance()
-    st = status_word(q.device)
-    rc = lib.capamd_drmmtks_train_step(_ptr(q), _ptr(dp), _ptr(dn), _ptr(idf), B, Q, L, _ptr(packed), V, D, int(topk), _ptr(adam.table), int(bool(softmax)),
-                                       step_size, omb1, b2, eps, bc2s, _ptr(loss), _ptr(ws), ws.numel(), _ptr(st.t), _stream())
-    _lib.check(rc, "capamd_drmmtks_train_step")
-    adam.commit()
-    if check:
-        st.raise_if_set()
-    return loss
+    lead = (_ptr(q), _ptr(dp), _ptr(dn), _ptr(idf), B, Q, L, _ptr(packed), V, D, int(topk), _ptr(adam.table))
+    return _train_step("capamd_drmmtks_train_step", lead, _lib.load().capamd_drmmtks_train_step_workspace_floats(B, Q, int(topk)), adam, softmax,
+                       q.device, check)
 
 
 def knrm_features(query, doc, packed, V, D, mu, sigma, need_grad=True, check=True):

@@ -111,14 +111,9 @@ class ConvKNRM_class(nn.Module):
         for conv in self.convs:
             params += [conv[0].weight, conv[0].bias]
         params += [lin.weight, lin.bias]
-        hit = self.__dict__.get("_adam_step")
-        if hit is None or hit.optimizer is not optimizer or hit.key[: len(params)] != tuple(p.data_ptr() for p in params) or not hit.still_valid():
-            hit = self.__dict__["_adam_step"] = engine.AdamStep(optimizer, params)
-        loss = engine.convknrm_train_step(d["query"], d["posdoc"], d["negdoc"], self.embeddings.weight, G, nf, len(ks), bool(self.p["crossmatch"]), hit,
-                                          bool(self.p["scoretanh"]), softmax)
-        with torch.no_grad():
-            torch._foreach_mul_(hit.trained, 1.0)          # (exact no-op: the kernels wrote the parameters behind autograd's back)
-        return loss[0]
+        hit = engine.AdamStep.cached(self, optimizer, params)
+        return engine.convknrm_train_step(d["query"], d["posdoc"], d["negdoc"], self.embeddings.weight, G, nf, len(ks), bool(self.p["crossmatch"]), hit,
+                                          bool(self.p["scoretanh"]), softmax)[0]
 
     def _forward_train_aten(self, sentence, query_sentence):
         """The reference's arithmetic (ConvKNRM.py:42-77, common.py:195-221) as ATen ops under autograd: the checker of the HIP

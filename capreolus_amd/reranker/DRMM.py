@@ -65,15 +65,10 @@ class DRMM_class(nn.Module):
             return None
         params = [self.ffw[0].weight, self.ffw[0].bias, self.ffw[2].weight, self.ffw[2].bias, self.gates.weight, self.output_layer.weight,
                   self.output_layer.bias]
-        hit = self.__dict__.get("_adam_step")
-        if hit is None or hit.optimizer is not optimizer or hit.key[: len(params)] != tuple(p.data_ptr() for p in params) or not hit.still_valid():
-            hit = self.__dict__["_adam_step"] = engine.AdamStep(optimizer, params)
+        hit = engine.AdamStep.cached(self, optimizer, params)
         w = self.embedding.weight
-        loss = engine.drmm_train_step(d["query"], d["posdoc"], d["negdoc"], d["query_idf"], self._packed.get(w), w.shape[0], w.shape[1],
-                                      self._bin_edges(w.device), self.hist_type, self.nodes, hit, softmax)
-        with torch.no_grad():
-            torch._foreach_mul_(hit.trained, 1.0)          # (exact no-op: the kernel wrote the parameters behind autograd's back)
-        return loss[0]
+        return engine.drmm_train_step(d["query"], d["posdoc"], d["negdoc"], d["query_idf"], self._packed.get(w), w.shape[0], w.shape[1],
+                                      self._bin_edges(w.device), self.hist_type, self.nodes, hit, softmax)[0]
 
     def _forward_train(self, sentence, query_sentence, query_idf):
         """Training step: the matching histogram (everything that touches [B, Q, L]) is the HIP kernel and has no

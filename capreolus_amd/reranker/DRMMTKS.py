@@ -52,15 +52,10 @@ class DRMMTKS_class(nn.Module):
         if d["query"].shape[0] > 1024 or self.embedding.weight.requires_grad:
             return None
         params = [self.ffw[0].weight, self.ffw[0].bias, self.gates.weight, self.output_layer.weight, self.output_layer.bias]
-        hit = self.__dict__.get("_adam_step")
-        if hit is None or hit.optimizer is not optimizer or hit.key[: len(params)] != tuple(p.data_ptr() for p in params) or not hit.still_valid():
-            hit = self.__dict__["_adam_step"] = engine.AdamStep(optimizer, params)
+        hit = engine.AdamStep.cached(self, optimizer, params)
         w = self.embedding.weight
-        loss = engine.drmmtks_train_step(d["query"], d["posdoc"], d["negdoc"], d["query_idf"], self._packed.get(w), w.shape[0], w.shape[1], self.topk, hit,
-                                         softmax)
-        with torch.no_grad():
-            torch._foreach_mul_(hit.trained, 1.0)          # (exact no-op: the kernel wrote the parameters behind autograd's back)
-        return loss[0]
+        return engine.drmmtks_train_step(d["query"], d["posdoc"], d["negdoc"], d["query_idf"], self._packed.get(w), w.shape[0], w.shape[1], self.topk, hit,
+                                         softmax)[0]
 
     def _forward_train(self, doc, query, query_idf):
         """Training step (reference trainer/pytorch.py:96-99 -> DRMMTKS.score): the gather / similarity / top-k - everything that

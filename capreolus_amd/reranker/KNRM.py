@@ -115,15 +115,10 @@ class KNRM_class(nn.Module):
         ks = list(self.kernels.kernels)
         lin = self.combine[0]
         params = [k.mu for k in ks] + [k.sigma for k in ks] + [lin.weight, lin.bias]
-        hit = self.__dict__.get("_adam_step")
-        if hit is None or hit.optimizer is not optimizer or hit.key[: len(params)] != tuple(p.data_ptr() for p in params) or not hit.still_valid():
-            hit = self.__dict__["_adam_step"] = engine.AdamStep(optimizer, params)
+        hit = engine.AdamStep.cached(self, optimizer, params)
         w = self.embedding.weight
-        loss = engine.knrm_train_step(d["query"], d["posdoc"], d["negdoc"], self._packed.get(w), w.shape[0], w.shape[1], len(ks), hit,
-                                      bool(self.p["gradkernels"]), bool(self.p["scoretanh"]), softmax)
-        with torch.no_grad():
-            torch._foreach_mul_(hit.trained, 1.0)          # (exact no-op: the kernel wrote the parameters behind autograd's back)
-        return loss[0]
+        return engine.knrm_train_step(d["query"], d["posdoc"], d["negdoc"], self._packed.get(w), w.shape[0], w.shape[1], len(ks), hit,
+                                      bool(self.p["gradkernels"]), bool(self.p["scoretanh"]), softmax)[0]
 
     def forward_indexed(self, store, pair_q, pair_d):
         """Scores (query row, document row) pairs of a device-resident `CandidateStore` -> [B]."""

@@ -102,15 +102,10 @@ class PACRR_class(nn.Module):
         for m in self.ngrams:
             params += [m.conv.weight, m.conv.bias]
         params += [self.linear1.weight, self.linear1.bias, self.linear2.weight, self.linear2.bias, self.linear3.weight, self.linear3.bias]
-        hit = self.__dict__.get("_adam_step")
-        if hit is None or hit.optimizer is not optimizer or hit.key[: len(params)] != tuple(t.data_ptr() for t in params) or not hit.still_valid():
-            hit = self.__dict__["_adam_step"] = engine.AdamStep(optimizer, params)
+        hit = engine.AdamStep.cached(self, optimizer, params)
         w = self.embedding.weight
-        loss = engine.pacrr_train_step(d["query"], d["posdoc"], d["negdoc"], d["query_idf"], self._packed.get(w), w.shape[0], w.shape[1], p["mingram"],
-                                       p["maxgram"], p["nfilters"], p["kmax"], p["idf"], p["combine"], p["nonlinearity"], hit, softmax)
-        with torch.no_grad():
-            torch._foreach_mul_(hit.trained, 1.0)          # (exact no-op: the kernels wrote the parameters behind autograd's back)
-        return loss[0]
+        return engine.pacrr_train_step(d["query"], d["posdoc"], d["negdoc"], d["query_idf"], self._packed.get(w), w.shape[0], w.shape[1], p["mingram"],
+                                       p["maxgram"], p["nfilters"], p["kmax"], p["idf"], p["combine"], p["nonlinearity"], hit, softmax)[0]
 
     def _forward_train_aten(self, doc, query, query_idf):
         """The trainable stage as the reference's ATen op sequence under autograd on the HIP similarity matrix: the checker of the

@@ -322,17 +322,16 @@ class PytorchTrainer:
                 done = self._fused_step(reranker, batch)
                 if done is None:
                     # the reranker's device step does not cover this configuration (engine.AdamStep: an optimizer parameter it does not
-                    # update, a batch it cannot take): the captured-graph route is the second choice - from this batch on, not eager
-                    # steps for the rest of training
-                    fused = self._use_fused = False
-                    graphed = self._graph_allowed()
-            if done is None and graphed and not fused:
+                    # update, a batch it cannot take): eager steps with the same optimizer from this batch on
+                    fused = graphed = self._use_fused = False
+                    self._graph_failed = True        # the fused route's plain (non-capturable) Adam cannot be captured
+            if done is None and graphed:
                 done = self._graphed_step(reranker, batch)
                 replayed = replayed or done is not None
             if done is not None:
                 losses.append(done)
             else:
-                if graphed and not fused and since_update == 0:
+                if graphed and since_update == 0:
                     # a batch the graph cannot take (another shape): after a replay every p.grad IS the graph's static gradient tensor,
                     # still holding the previous step's values - backward() would add to them
                     self.optimizer.zero_grad(set_to_none=True)

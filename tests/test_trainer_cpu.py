@@ -388,6 +388,53 @@ def pickle_load(fn):
         return pickle.load(f)
 
 
+class _FusedLinearReranker(_LinearReranker):
+    """A device training step (here: an eager step with the trainer's optimizer) that declines from the third batch on."""
+
+    def __init__(self):
+        super().__init__()
+        self.fused_calls = 0
+
+    def fused_train_step(self, d, optimizer, softmax=False):
+        self.fused_calls += 1
+        if self.fused_calls >= 3:
+            return None
+        optimizer.zero_grad()
+        pos, neg = self.score(d)
+        loss = PytorchTrainer.pair_hinge_loss((pos, neg))
+        loss.backward()
+        optimizer.step()
+        return loss.detach()
+
+
+def test_declined_fused_step_trains_eagerly_without_a_capture(tmp_path, monkeypatch):
+    """When the fused step returns None mid-run, the rest of training takes eager steps with the plain Adam the fused route built:
+    that optimizer cannot be captured, so no graph capture is tried - not in this iteration, not in a later one."""
+    s = FakeSampler(3)
+    qrels = {q: {d: (i % 3) for i, d in enumerate(ds)} for q, ds in s.qid_to_docids.items()}
+
+    def no_capture(*a, **k):
+        raise AssertionError("a graph capture was attempted with the fused route's plain Adam")
+
+    monkeypatch.setattr(PytorchTrainer, "_fused_allowed", lambda self, reranker: True)
+    monkeypatch.setattr(PytorchTrainer, "_graph_allowed", lambda self: not getattr(self, "_graph_failed", False))
+    monkeypatch.setattr(PytorchTrainer, "_capture_train_step", no_capture)
+    steps = []
+    step = torch.optim.Adam.step
+
+    def spy(self, *a, **k):
+        steps.append(self.param_groups[0]["lr"])
+        return step(self, *a, **k)
+
+    monkeypatch.setattr(torch.optim.Adam, "step", spy)
+    t, r = PytorchTrainer({"batch": 4, "itersize": 16, "niters": 2, "lr": 0.01, "evalbatch": 8}), _FusedLinearReranker()
+    losses = t.train(r, _PairData(), tmp_path / "train", s, tmp_path / "dev", qrels, "ndcg_cut_20")
+    assert len(losses) == 2 and all(np.isfinite(losses))
+    assert r.fused_calls == 3                       # two fused steps, the declined third batch, then never again
+    assert len(steps) == 2 * 4                      # every batch of both iterations took one optimizer step
+    assert not t._use_fused and t._graph_failed and t._train_graph is None
+
+
 @pytest.mark.parametrize("mode,exact,expect_lists", [("exact", True, True), ("exact", False, False), ("always", False, True), ("never", True, False)])
 def test_resident_scoring_picks_lists_by_option(mode, exact, expect_lists):
     """`PytorchTrainer._score_store` (predict / predict_resident / evaluate_resident on a candidate store): whole candidate lists for the
