@@ -238,6 +238,11 @@ _LAYER_TENSORS = (
 SUPPORTED_LENGTHS = tuple(range(32, 257, 32)) + (384, 512)   # the attention kernels of the library (capamd_bert_maxp_forward)
 
 
+def _shorter_lengths(S, skip_padding, min_len=0):
+    """the lengths above `min_len` a passage of S tokens may be encoded at instead (BertEngine._by_length)"""
+    return [x for x in SUPPORTED_LENGTHS if min_len < x < S] if (skip_padding and S in SUPPORTED_LENGTHS) else []
+
+
 class BertEngine:
     """Device-side state of one BERT sequence classifier for capamd_bert_maxp_forward.
 
@@ -315,23 +320,74 @@ class BertEngine:
         self._blob, self._lf32, self._keep, self._model, self._key = blob, lf32, keep, m, key
         return m
 
-    def _encode(self, ids, mask, seg, B, P, S, aggregation, out, plog, check, ws_key=None):
-        """One capamd_bert_maxp_forward call over [B, P, S] (all passages at length S) on the current stream; `ws_key` selects
-        the workspace (one per concurrently running stream)."""
+    def _workspace(self, key, S, n, device):
+        """(model, workspace, micro-batch) of one encoder call over n passages of length S; `key` selects the workspace (one per
+        concurrently running stream), which only ever grows."""
         m = self.model()
-        lib = _lib.load()
         # `microbatch` counts passages of 256 tokens: shorter passages go in proportionally larger micro-batches (same rows, same
         # workspace, and the GEMMs of a short-passage bucket still see 65,536 rows)
-        mb = min(self.microbatch * max(1, 256 // S), B * P)
-        need = lib.capamd_bert_workspace_bytes(ctypes.byref(m), S, mb, B * P)
+        mb = min(self.microbatch * max(1, 256 // S), n)
+        need = _lib.load().capamd_bert_workspace_bytes(ctypes.byref(m), S, mb, n)
         if need < 0:
             raise ValueError(f"unsupported passage length {S} (supported: multiples of 32 up to 256, 384, 512)")
-        ws = self._wss.get(ws_key)
-        if ws is None or ws.numel() < need or ws.device != ids.device:
-            ws = self._wss[ws_key] = torch.empty(need, dtype=torch.uint8, device=ids.device)
+        ws = self._wss.get(key)
+        if ws is None or ws.numel() < need or ws.device != device:
+            ws = self._wss[key] = torch.empty(need, dtype=torch.uint8, device=device)
+        return m, ws, mb
+
+    def _side_stream(self, key, device):
+        side = self._streams.get(key)
+        if side is None:
+            side = self._streams[key] = torch.cuda.Stream(device=device)
+        return side
+
+    def _by_length(self, ids, mask, seg, lengths, run, extras=(), outs=()):
+        """Runs an encoder entry over the passages [NP, S] x3, each at the shortest of `lengths` (ascending, all < S; else S) that holds
+        its last attended token.  `run(ids, mask, seg, S, extras, outs, ws_key)` makes the one library call on the current stream;
+        `extras` are further per-passage inputs, `outs` (tensor, dim) pairs whose dimension `dim` counts the passages.  The buckets are
+        independent: each runs on its own stream with its own workspace, so one bucket's kernels fill the CUs another bucket's last
+        tiles leave idle and the launch gaps of one hide behind the work of the others.  Without `lengths`: one call on the caller's
+        stream, writing straight into `outs`.  The caller has called model() on its stream: the (re)pack precedes the fan-out."""
+        NP, S = ids.shape
+        dev = ids.device
+        if not lengths:
+            run(ids, mask, seg, S, extras, [t for t, _ in outs], None)
+            return
+        # position after the last attended token of each passage (masks with holes keep their full extent)
+        end = ((mask != 0) * torch.arange(1, S + 1, device=dev)).amax(dim=1)
+        bounds = lengths + [S]
+        bucket = torch.bucketize(end, torch.tensor(lengths, device=dev), right=False)   # 0: <= lengths[0], ...
+        order = torch.argsort(bucket, stable=True)
+        counts = torch.bincount(bucket, minlength=len(bounds)).cpu().tolist()   # the one host round trip of this call
+        main = torch.cuda.current_stream(dev)
+        lo, used = 0, []
+        for Sb, n in zip(bounds, counts):
+            if n == 0:
+                continue
+            sel = order[lo:lo + n]
+            lo += n
+            side = self._side_stream(Sb, dev)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                # (a ragged bucket is padded to whole 256-row GEMM tiles inside the library)
+                bi, bm, bs = (t.index_select(0, sel)[:, :Sb].contiguous() for t in (ids, mask, seg))
+                extras_b = [t.index_select(0, sel) for t in extras]
+                outs_b = [torch.empty(t.shape[:dim] + (n,) + t.shape[dim + 1:], dtype=t.dtype, device=dev) for t, dim in outs]
+                run(bi, bm, bs, Sb, extras_b, outs_b, Sb)
+                for (t, dim), t_b in zip(outs, outs_b):
+                    t.index_copy_(dim, sel, t_b)
+                for t in (bi, bm, bs, *extras_b, *outs_b, sel):
+                    t.record_stream(side)
+            used.append(side)
+        for side in used:
+            main.wait_stream(side)
+
+    def _encode(self, ids, mask, seg, B, P, S, aggregation, out, plog, check, ws_key=None):
+        """One capamd_bert_maxp_forward call over [B, P, S] (all passages at length S) on the current stream."""
+        m, ws, mb = self._workspace(ws_key, S, B * P, ids.device)
         st = status_word(ids.device)
-        rc = lib.capamd_bert_maxp_forward(_ptr(ids), _ptr(mask), _ptr(seg), B, P, S, ctypes.byref(m), AGGREGATIONS[aggregation], mb,
-                                          _ptr(ws), ws.numel(), _ptr(out), _ptr(plog), _ptr(st.t), _stream())
+        rc = _lib.load().capamd_bert_maxp_forward(_ptr(ids), _ptr(mask), _ptr(seg), B, P, S, ctypes.byref(m), AGGREGATIONS[aggregation], mb,
+                                                  _ptr(ws), ws.numel(), _ptr(out), _ptr(plog), _ptr(st.t), _stream())
         _lib.check(rc, "capamd_bert_maxp_forward")
         if check:
             st.raise_if_set()
@@ -357,9 +413,17 @@ class BertEngine:
         if aggregation == "first" and not return_passage_logits and P > 1 and skip_padding:
             # ptBERTMaxP.py:85-86 takes scores[:, 0]: the other passages of a document are never read
             return self.forward(ids[:, :1], mask[:, :1], seg[:, :1], "first", False, check, skip_padding)
-        lengths = [x for x in SUPPORTED_LENGTHS if x < S] if (skip_padding and S in SUPPORTED_LENGTHS) else []
-        if not lengths:
-            NP = B * P
+        NP = B * P
+        fids, fmask, fseg = ids.view(NP, S), mask.view(NP, S), seg.view(NP, S)
+        lengths = _shorter_lengths(S, skip_padding)
+        if lengths:
+            def run(bi, bm, bs, Sb, _, outs_b, ws_key):
+                self._encode(bi, bm, bs, bi.shape[0], 1, Sb, "first", outs_b[0], None, False, ws_key=ws_key)
+
+            plog = torch.empty(NP, dtype=torch.float32, device=ids.device)
+            self.model()
+            self._by_length(fids, fmask, fseg, lengths, run, outs=[(plog, 0)])
+        else:
             q = 256 // math.gcd(S, 256)                      # passages per whole 256-row GEMM tile
             ns = max(1, min(self.n_streams, NP // self.microbatch))
             per = (NP // ns + q - 1) // q * q if ns > 1 else NP   # passages per stream, in whole tiles
@@ -376,63 +440,18 @@ class BertEngine:
                 return (out, plog) if return_passage_logits else out
             # full-length computation of a large batch: `ns` slices on as many streams (own workspaces) - the persistent GEMM kernels
             # of one slice start on the CUs the others' last tiles, low-occupancy kernels and launch gaps leave idle
-            fids, fmask, fseg = ids.view(NP, S), mask.view(NP, S), seg.view(NP, S)
             plog = torch.empty(NP, dtype=torch.float32, device=ids.device)
             self.model()
             main = torch.cuda.current_stream(ids.device)
             sides = []
             for k, (a0, a1) in enumerate(zip(cuts[:-1], cuts[1:])):
-                side = self._streams.get(("half", k))
-                if side is None:
-                    side = self._streams[("half", k)] = torch.cuda.Stream(device=ids.device)
+                side = self._side_stream(("half", k), ids.device)
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
                     self._encode(fids[a0:a1], fmask[a0:a1], fseg[a0:a1], a1 - a0, 1, S, "first", plog[a0:a1], None, False, ws_key=("half", k))
                 sides.append(side)
             for side in sides:
                 main.wait_stream(side)
-            if check:
-                status_word(ids.device).raise_if_set()
-            cnt = torch.empty(1, dtype=torch.int32, device=ids.device)
-            _lib.check(_lib.load().capamd_maxp_pool(_ptr(plog), _ptr(mask), _ptr(seg), B, P, S, AGGREGATIONS[aggregation], _ptr(out), _ptr(cnt),
-                                                    _stream()), "capamd_maxp_pool")
-            return (out, plog) if return_passage_logits else out
-
-        NP = B * P
-        fids, fmask, fseg = ids.view(NP, S), mask.view(NP, S), seg.view(NP, S)
-        # position after the last attended token of each passage (masks with holes keep their full extent)
-        end = ((fmask != 0) * torch.arange(1, S + 1, device=ids.device)).amax(dim=1)
-        bounds = lengths + [S]
-        bucket = torch.bucketize(end, torch.tensor(lengths, device=ids.device), right=False)   # 0: <= lengths[0], ...
-        order = torch.argsort(bucket, stable=True)
-        counts = torch.bincount(bucket, minlength=len(bounds)).cpu().tolist()   # the one host round trip of this call
-        plog = torch.empty(NP, dtype=torch.float32, device=ids.device)
-        self.model()                                  # (re)pack on the caller's stream before the buckets fan out
-        main = torch.cuda.current_stream(ids.device)
-        lo = 0
-        used = []
-        for Sb, n in zip(bounds, counts):
-            if n == 0:
-                continue
-            sel = order[lo:lo + n]
-            lo += n
-            # the buckets are independent: each runs on its own stream with its own workspace, so one bucket's kernels fill the
-            # CUs another bucket's last tiles leave idle and the launch gaps of one hide behind the work of the others
-            side = self._streams.get(Sb)
-            if side is None:
-                side = self._streams[Sb] = torch.cuda.Stream(device=ids.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                # (a ragged bucket is padded to whole 256-row GEMM tiles inside capamd_bert_maxp_forward)
-                bi, bm, bs = (t.index_select(0, sel)[:, :Sb].contiguous() for t in (fids, fmask, fseg))
-                o = torch.empty(n, dtype=torch.float32, device=ids.device)
-                self._encode(bi, bm, bs, n, 1, Sb, "first", o, None, False, ws_key=Sb)
-                plog.index_copy_(0, sel, o)
-                for t in (bi, bm, bs, o, sel):
-                    t.record_stream(side)
-            used.append(side)
-        for side in used:
-            main.wait_stream(side)
         if check:
             status_word(ids.device).raise_if_set()
         cnt = torch.empty(1, dtype=torch.int32, device=ids.device)
@@ -493,14 +512,15 @@ LISTS_WORKSPACE_BUDGET = 2 << 30
 LISTS_MAX_QLEN = 8          # query terms a whole-list call takes (csrc/lists.h: kListMaxQ; PACRR: 4)
 
 
-def _lists_workspace(device, n_lists, V, n_pairs, L, Q=4):
-    lib = _lib.load()
-    one = int(lib.capamd_lists_workspace_bytes_q(1, int(V), 0, int(L), int(Q)))
-    per_list = int(lib.capamd_lists_workspace_bytes_q(2, int(V), 0, int(L), int(Q))) - one
+def _lists_workspace(device, n_lists, nbytes_of, refusal):
+    """The workspace of a whole-list call on the current stream, exactly as many bytes as the library asks for the lists kept in flight;
+    `nbytes_of(k)`: what it asks for k of them (0: it does not take the geometry - ValueError(refusal))."""
+    one = int(nbytes_of(1))
+    if one == 0:
+        raise ValueError(refusal)
+    per_list = int(nbytes_of(2)) - one
     in_flight = max(1, min(int(n_lists), LISTS_WORKSPACE_BUDGET // max(per_list, 1)))
-    nbytes = int(lib.capamd_lists_workspace_bytes_q(in_flight, int(V), int(n_pairs), int(L), int(Q)))
-    if nbytes == 0:
-        raise ValueError(f"whole-list scoring takes queries of up to {LISTS_MAX_QLEN} terms, got {Q}")
+    nbytes = int(nbytes_of(in_flight))
     key = (device.index, int(torch.cuda.current_stream(device).cuda_stream))
     ws = _list_workspaces.get(key)
     if ws is None or ws.numel() < nbytes:
@@ -532,21 +552,35 @@ def _lists_ids(query, doc, store, pair_q, pair_d):
     return q, d, None, None, None, None, q.shape[0], q.shape[1], d.shape[1], q.device
 
 
-def knrm_forward_lists(offsets, packed, V, D, mu, sigma, w1, b1, w2=None, b2=None, scoretanh=False, query=None, doc=None, store=None, pair_q=None,
-                       pair_d=None, out=None, check=True):
-    """KNRM over whole candidate lists (capamd_knrm_forward_lists): pairs laid out list after list, `offsets` their n_lists + 1
-    boundaries on the host; ids as [B, Q] / [B, L] tensors or through a CandidateStore (store, pair_q, pair_d)."""
-    q, d, qt, dt, pq, pd, B, Q, L, dev = _lists_ids(query, doc, store, pair_q, pair_d)
-    _need_gpu(packed, mu, sigma, w1, b1, w2, b2)
+def _lists_pair_workspace(device, n_lists, V, n_pairs, L, Q=4):
+    """_lists_workspace of the entries of csrc/lists.hip (capamd_lists_workspace_bytes_q; n_pairs = 0: without the per-pair part)"""
+    lib = _lib.load()
+    return _lists_workspace(device, n_lists, lambda k: lib.capamd_lists_workspace_bytes_q(k, int(V), int(n_pairs), int(L), int(Q)),
+                            f"whole-list scoring takes queries of up to {LISTS_MAX_QLEN} terms, got {Q}")
+
+
+def _lists_call(offsets, query, doc, store, pair_q, pair_d, out, params):
+    """What every whole-list wrapper starts with -> (the six id tensors of _lists_ids, host offsets, B, Q, L, device, out [B]);
+    `params`: the call's other tensors, which must be on the device."""
+    *ids, B, Q, L, dev = _lists_ids(query, doc, store, pair_q, pair_d)
+    _need_gpu(*params)
     off = _list_offsets(offsets)
     if int(off[-1]) != B:
         raise ValueError("the last list offset must be the number of pairs")
     if out is None:
         out = torch.empty(B, dtype=torch.float32, device=dev)
+    return ids, off, B, Q, L, dev, out
+
+
+def knrm_forward_lists(offsets, packed, V, D, mu, sigma, w1, b1, w2=None, b2=None, scoretanh=False, query=None, doc=None, store=None, pair_q=None,
+                       pair_d=None, out=None, check=True):
+    """KNRM over whole candidate lists (capamd_knrm_forward_lists): pairs laid out list after list, `offsets` their n_lists + 1
+    boundaries on the host; ids as [B, Q] / [B, L] tensors or through a CandidateStore (store, pair_q, pair_d)."""
+    ids, off, B, Q, L, dev, out = _lists_call(offsets, query, doc, store, pair_q, pair_d, out, (packed, mu, sigma, w1, b1, w2, b2))
     hidden = 0 if w2 is None else w1.shape[0]
-    st, ws = status_word(dev), _lists_workspace(dev, off.size - 1, V, B, L, Q)
+    st, ws = status_word(dev), _lists_pair_workspace(dev, off.size - 1, V, B, L, Q)
     rc = _lib.load().capamd_knrm_forward_lists(
-        _ptr(q), _ptr(d), _ptr(qt), _ptr(dt), _ptr(pq), _ptr(pd), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(packed), V, D, _ptr(mu),
+        *map(_ptr, ids), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(packed), V, D, _ptr(mu),
         _ptr(sigma), mu.numel(), _ptr(w1), _ptr(b1), hidden, _ptr(w2), _ptr(b2), int(bool(scoretanh)), _ptr(out), _ptr(st.t), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, "capamd_knrm_forward_lists")
     if check:
@@ -557,18 +591,12 @@ def knrm_forward_lists(offsets, packed, V, D, mu, sigma, w1, b1, w2=None, b2=Non
 def drmm_forward_lists(offsets, idf, packed, V, D, edges, hist_type, gate_type, gate_w, emb_raw, w1, b1, w2, b2, out_w, out_b, query=None, doc=None,
                        store=None, pair_q=None, pair_d=None, out=None, counts_out=None, check=True):
     """DRMM over whole candidate lists (capamd_drmm_forward_lists); `idf`: [B, Q] per pair, or the store's [NQ, Q] table in indexed mode."""
-    q, d, qt, dt, pq, pd, B, Q, L, dev = _lists_ids(query, doc, store, pair_q, pair_d)
-    _need_gpu(packed, edges, gate_w, w1, b1, w2, b2, out_w, out_b)
-    off = _list_offsets(offsets)
-    if int(off[-1]) != B:
-        raise ValueError("the last list offset must be the number of pairs")
+    ids, off, B, Q, L, dev, out = _lists_call(offsets, query, doc, store, pair_q, pair_d, out, (packed, edges, gate_w, w1, b1, w2, b2, out_w, out_b))
     idf = _f32(idf)
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=dev)
     ld = emb_raw.stride(0) if emb_raw is not None else 0
-    st, ws = status_word(dev), _lists_workspace(dev, off.size - 1, V, B, L, Q)
+    st, ws = status_word(dev), _lists_pair_workspace(dev, off.size - 1, V, B, L, Q)
     rc = _lib.load().capamd_drmm_forward_lists(
-        _ptr(q), _ptr(d), _ptr(qt), _ptr(dt), _ptr(pq), _ptr(pd), _ptr(idf), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(packed), V, D,
+        *map(_ptr, ids), _ptr(idf), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(packed), V, D,
         _ptr(edges), edges.numel(), HIST_TYPES[hist_type], GATE_TYPES[gate_type], _ptr(gate_w), _ptr(emb_raw), ld, _ptr(w1), _ptr(b1), w1.shape[0],
         _ptr(w2), _ptr(b2), _ptr(out_w), _ptr(out_b), _ptr(out), _ptr(counts_out), _ptr(st.t), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, "capamd_drmm_forward_lists")
@@ -958,19 +986,13 @@ def drmmtks_forward(query, doc, idf, packed, V, D, topk, gate_w, ffw_w, ffw_b, o
 def drmmtks_forward_lists(offsets, idf, packed, V, D, topk, gate_w, ffw_w, ffw_b, out_w, out_b, query=None, doc=None, store=None, pair_q=None,
                           pair_d=None, out=None, check=True):
     """DRMM-TKS over whole candidate lists (capamd_drmmtks_forward_lists); `idf`: [B, Q] per pair, or the store's [NQ, Q] table."""
-    q, d, qt, dt, pq, pd, B, Q, L, dev = _lists_ids(query, doc, store, pair_q, pair_d)
-    _need_gpu(packed, gate_w, ffw_w, ffw_b, out_w, out_b)
-    off = _list_offsets(offsets)
-    if int(off[-1]) != B:
-        raise ValueError("the last list offset must be the number of pairs")
+    ids, off, B, Q, L, dev, out = _lists_call(offsets, query, doc, store, pair_q, pair_d, out, (packed, gate_w, ffw_w, ffw_b, out_w, out_b))
     if topk > L:
         raise RuntimeError("selected index k out of range")  # what torch.topk raises at DRMMTKS.py:56
     idf = _f32(idf)
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=dev)
-    st, ws = status_word(dev), _lists_workspace(dev, off.size - 1, V, B, L, Q)
+    st, ws = status_word(dev), _lists_pair_workspace(dev, off.size - 1, V, B, L, Q)
     rc = _lib.load().capamd_drmmtks_forward_lists(
-        _ptr(q), _ptr(d), _ptr(qt), _ptr(dt), _ptr(pq), _ptr(pd), _ptr(idf), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(packed), V, D,
+        *map(_ptr, ids), _ptr(idf), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(packed), V, D,
         int(topk), _ptr(gate_w), _ptr(ffw_w), _ptr(ffw_b), _ptr(out_w), _ptr(out_b), _ptr(out), _ptr(st.t), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, "capamd_drmmtks_forward_lists")
     if check:
@@ -1025,19 +1047,13 @@ def pacrr_forward_lists(offsets, idf, packed, V, D, mingram, maxgram, nfilters, 
     """PACRR over whole candidate lists (capamd_pacrr_forward_lists); `idf`: [B, Q] per pair, or the store's [NQ, Q] table.
     `pair_part=False` hands the library a workspace without the per-pair part (capamd_lists_workspace_bytes with n_pairs = 0): the combine
     layers then run at the end of every pair's convolution workgroup instead of in one pass behind them - the same scores, bit for bit."""
-    q, d, qt, dt, pq, pd, B, Q, L, dev = _lists_ids(query, doc, store, pair_q, pair_d)
-    _need_gpu(packed, conv_w, conv_b, w1, b1, w2, b2, w3, b3)
-    off = _list_offsets(offsets)
-    if int(off[-1]) != B:
-        raise ValueError("the last list offset must be the number of pairs")
+    ids, off, B, Q, L, dev, out = _lists_call(offsets, query, doc, store, pair_q, pair_d, out, (packed, conv_w, conv_b, w1, b1, w2, b2, w3, b3))
     if kmax > L:
         raise RuntimeError("selected index k out of range")  # what torch.topk raises at PACRR.py:74
     idf = _f32(idf)
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=dev)
-    st, ws = status_word(dev), _lists_workspace(dev, off.size - 1, V, B if pair_part else 0, L)
+    st, ws = status_word(dev), _lists_pair_workspace(dev, off.size - 1, V, B if pair_part else 0, L)
     rc = _lib.load().capamd_pacrr_forward_lists(
-        _ptr(q), _ptr(d), _ptr(qt), _ptr(dt), _ptr(pq), _ptr(pd), _ptr(idf), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(packed), V, D,
+        *map(_ptr, ids), _ptr(idf), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(packed), V, D,
         int(mingram), int(maxgram), int(nfilters), int(kmax), _ptr(conv_w), _ptr(conv_b), int(bool(use_idf)), w1.shape[0], NONLINEARITIES[nonlinearity],
         _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(w3), _ptr(b3), _ptr(out), _ptr(st.t), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, "capamd_pacrr_forward_lists")
@@ -1098,33 +1114,16 @@ def convknrm_forward_lists(offsets, query, doc, tables, V, maxngram, filters, cr
                            check=True):
     """ConvKNRM over whole candidate lists (capamd_convknrm_forward_lists): pairs laid out list after list, `offsets` their n_lists + 1
     boundaries on the host; the unigram document view once per distinct token of a list.  Scores equal convknrm_forward's bit for bit."""
-    _need_gpu(query, doc, tables, mu, sigma, w1, b1)
-    q, d = _i64(query), _i64(doc)
-    B, Q = q.shape
-    L = d.shape[1]
-    off = _list_offsets(offsets)
-    if int(off[-1]) != B:
-        raise ValueError("the last list offset must be the number of pairs")
-    if out is None:
-        out = torch.empty(B, dtype=torch.float32, device=q.device)
+    (q, d, *_), off, B, Q, L, dev, out = _lists_call(offsets, query, doc, None, None, None, out, (query, doc, tables, mu, sigma, w1, b1))
     lib = _lib.load()
-    n_lists = off.size - 1
-    one = int(lib.capamd_convknrm_lists_workspace_bytes(1, int(V), Q, int(maxngram), int(filters)))
-    if one == 0:
-        raise ValueError("capamd_convknrm_forward_lists does not take this geometry")
-    per_list = int(lib.capamd_convknrm_lists_workspace_bytes(2, int(V), Q, int(maxngram), int(filters))) - one
-    in_flight = max(1, min(n_lists, LISTS_WORKSPACE_BUDGET // max(per_list, 1)))
-    nbytes = int(lib.capamd_convknrm_lists_workspace_bytes(in_flight, int(V), Q, int(maxngram), int(filters)))
-    key = (q.device.index, int(torch.cuda.current_stream(q.device).cuda_stream))
-    ws = _list_workspaces.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = _list_workspaces[key] = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
-    st = status_word(q.device)
+    ws = _lists_workspace(dev, off.size - 1, lambda k: lib.capamd_convknrm_lists_workspace_bytes(k, int(V), Q, int(maxngram), int(filters)),
+                          "capamd_convknrm_forward_lists does not take this geometry")
+    st = status_word(dev)
     H = 0 if w2 is None else w1.shape[0]
-    rc = lib.capamd_convknrm_forward_lists(_ptr(q), _ptr(d), ctypes.c_void_p(off.ctypes.data), n_lists, Q, L, _ptr(tables), V, int(maxngram), int(filters),
+    rc = lib.capamd_convknrm_forward_lists(_ptr(q), _ptr(d), ctypes.c_void_p(off.ctypes.data), off.size - 1, Q, L, _ptr(tables), V, int(maxngram), int(filters),
                                            int(bool(crossmatch)), _ptr(mu), _ptr(sigma), mu.numel(), _ptr(w1), _ptr(b1), H,
                                            None if w2 is None else _ptr(w2), None if b2 is None else _ptr(b2), int(bool(score_tanh)), _ptr(out),
-                                           _ptr(st.t), _ptr(ws), nbytes, _stream())
+                                           _ptr(st.t), _ptr(ws), ws.numel(), _stream())
     _lib.check(rc, "capamd_convknrm_forward_lists")
     if check:
         st.raise_if_set()
@@ -1140,25 +1139,6 @@ class CedrEngine:
 
     def __init__(self, bert_engine):
         self.be = bert_engine
-        self._wss = {}
-        self._streams = {}
-
-    def _passages(self, ids, mask, seg, S, qm0, maxqlen, layers, mu, sigma, pk, cls, ws_key):
-        """One capamd_cedr_passage_features call over n passages of length S ([n, S] x3; qm0 [n, A]) on the current stream."""
-        m, lib = self.be.model(), _lib.load()
-        n = ids.shape[0]
-        mb = min(self.be.microbatch * max(1, 256 // S), n)
-        need = lib.capamd_bert_workspace_bytes(ctypes.byref(m), S, mb, n)
-        if need < 0:
-            raise ValueError(f"unsupported passage length {S} (supported: multiples of 32 up to 256, 384, 512)")
-        ws = self._wss.get(ws_key)
-        if ws is None or ws.numel() < need or ws.device != ids.device:
-            ws = self._wss[ws_key] = torch.empty(need, dtype=torch.uint8, device=ids.device)
-        arr = (ctypes.c_int * max(1, len(layers)))(*layers)
-        rc = lib.capamd_cedr_passage_features(_ptr(ids), _ptr(mask), _ptr(seg), n, 1, S, ctypes.byref(m), mb, _ptr(ws), ws.numel(), int(maxqlen),
-                                              _ptr(qm0), arr, len(layers), _ptr(mu), _ptr(sigma), mu.numel(), _ptr(pk), _ptr(cls),
-                                              _ptr(status_word(ids.device).t), _stream())
-        _lib.check(rc, "capamd_cedr_passage_features")
 
     def forward(self, doc_input, doc_mask, doc_seg, maxqlen, simmat_layers, mu, sigma, cls_mode, w1, b1, w2=None, b2=None, check=True,
                 return_features=False, skip_padding=None):
@@ -1192,40 +1172,18 @@ class CedrEngine:
         fids, fmask, fseg = ids.view(NP, S), mask.view(NP, S), seg.view(NP, S)
         if skip_padding is None:
             skip_padding = self.be.skip_padding
-        lengths = [x for x in SUPPORTED_LENGTHS if x < S and x > A + 1] if (skip_padding and S in SUPPORTED_LENGTHS) else []
-        if not lengths:
-            self._passages(fids, fmask, fseg, S, qm0, maxqlen, layers, mu, sigma, pk, cls, None)
-        else:
-            end = ((fmask != 0) * torch.arange(1, S + 1, device=dev)).amax(dim=1)
-            bounds = lengths + [S]
-            bucket = torch.bucketize(end, torch.tensor(lengths, device=dev), right=False)
-            order = torch.argsort(bucket, stable=True)
-            counts = torch.bincount(bucket, minlength=len(bounds)).cpu().tolist()   # the one host round trip of this call
-            main = torch.cuda.current_stream(dev)
-            lo, used = 0, []
-            for Sb, n in zip(bounds, counts):
-                if n == 0:
-                    continue
-                sel = order[lo:lo + n]
-                lo += n
-                side = self._streams.get(Sb)
-                if side is None:
-                    side = self._streams[Sb] = torch.cuda.Stream(device=dev)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    # (a ragged bucket is padded to whole GEMM tiles inside capamd_cedr_passage_features)
-                    bi, bm, bs = (t.index_select(0, sel)[:, :Sb].contiguous() for t in (fids, fmask, fseg))
-                    bq = qm0.index_select(0, sel)
-                    pk_b = torch.empty((max(1, n_sel), n, K * A), dtype=torch.float32, device=dev)
-                    cls_b = torch.empty((n, H), dtype=torch.float32, device=dev)
-                    self._passages(bi, bm, bs, Sb, bq, maxqlen, layers, mu, sigma, pk_b, cls_b, Sb)
-                    pk.index_copy_(1, sel, pk_b)
-                    cls.index_copy_(0, sel, cls_b)
-                    for t in (bi, bm, bs, bq, pk_b, cls_b, sel):
-                        t.record_stream(side)
-                used.append(side)
-            for side in used:
-                main.wait_stream(side)
+        arr = (ctypes.c_int * max(1, n_sel))(*layers)
+
+        def run(bi, bm, bs, Sb, extras_b, outs_b, ws_key):
+            (bq,), (pk_b, cls_b), n = extras_b, outs_b, bi.shape[0]
+            m, ws, mb = self.be._workspace(ws_key, Sb, n, dev)
+            rc = lib.capamd_cedr_passage_features(_ptr(bi), _ptr(bm), _ptr(bs), n, 1, Sb, ctypes.byref(m), mb, _ptr(ws), ws.numel(), int(maxqlen),
+                                                  _ptr(bq), arr, n_sel, _ptr(mu), _ptr(sigma), K, _ptr(pk_b), _ptr(cls_b),
+                                                  _ptr(status_word(dev).t), _stream())
+            _lib.check(rc, "capamd_cedr_passage_features")
+
+        # (a bucket must hold the query columns: Sb > maxqlen + 2)
+        self.be._by_length(fids, fmask, fseg, _shorter_lengths(S, skip_padding, A + 1), run, extras=[qm0], outs=[(pk, 1), (cls, 0)])
         n_in = (H if cls_mode else 0) + n_sel * K
         feats = torch.empty((B, n_in), dtype=torch.float32, device=dev) if return_features else None
         hidden = 0 if w2 is None else w1.shape[0]
@@ -1249,24 +1207,7 @@ class ParadeEngine:
     def __init__(self, bert_engine, ln_eps=1e-12):
         self.be = bert_engine
         self.ln_eps = float(ln_eps)
-        self._wss = {}
-        self._streams = {}
         self._head_ws = None
-
-    def _passages(self, ids, mask, seg, S, cls, ws_key):
-        """One capamd_parade_passage_cls call over n passages of length S ([n, S] x3) on the current stream."""
-        m, lib = self.be.model(), _lib.load()
-        n = ids.shape[0]
-        mb = min(self.be.microbatch * max(1, 256 // S), n)
-        need = lib.capamd_bert_workspace_bytes(ctypes.byref(m), S, mb, n)
-        if need < 0:
-            raise ValueError(f"unsupported passage length {S} (supported: multiples of 32 up to 256, 384, 512)")
-        ws = self._wss.get(ws_key)
-        if ws is None or ws.numel() < need or ws.device != ids.device:
-            ws = self._wss[ws_key] = torch.empty(need, dtype=torch.uint8, device=ids.device)
-        rc = lib.capamd_parade_passage_cls(_ptr(ids), _ptr(mask), _ptr(seg), n, 1, S, ctypes.byref(m), mb, _ptr(ws), ws.numel(), _ptr(cls),
-                                           _ptr(status_word(ids.device).t), _stream())
-        _lib.check(rc, "capamd_parade_passage_cls")
 
     def passage_cls(self, ids, mask, seg, skip_padding=None):
         """int64 [B, P, S] x3 -> fp32 [B * P, hidden]: the [CLS] rows of the last hidden state (ptparade.py:74).  skip_padding (default:
@@ -1280,36 +1221,15 @@ class ParadeEngine:
         fids, fmask, fseg = ids.view(NP, S), mask.view(NP, S), seg.view(NP, S)
         if skip_padding is None:
             skip_padding = self.be.skip_padding
-        lengths = [x for x in SUPPORTED_LENGTHS if x < S] if (skip_padding and S in SUPPORTED_LENGTHS) else []
-        if not lengths:
-            self._passages(fids, fmask, fseg, S, cls, None)
-            return cls
-        end = ((fmask != 0) * torch.arange(1, S + 1, device=dev)).amax(dim=1)
-        bounds = lengths + [S]
-        bucket = torch.bucketize(end, torch.tensor(lengths, device=dev), right=False)
-        order = torch.argsort(bucket, stable=True)
-        counts = torch.bincount(bucket, minlength=len(bounds)).cpu().tolist()   # the one host round trip of this call
-        main = torch.cuda.current_stream(dev)
-        lo, used = 0, []
-        for Sb, n in zip(bounds, counts):
-            if n == 0:
-                continue
-            sel = order[lo:lo + n]
-            lo += n
-            side = self._streams.get(Sb)
-            if side is None:
-                side = self._streams[Sb] = torch.cuda.Stream(device=dev)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                bi, bm, bs = (t.index_select(0, sel)[:, :Sb].contiguous() for t in (fids, fmask, fseg))
-                cls_b = torch.empty((n, H), dtype=torch.float32, device=dev)
-                self._passages(bi, bm, bs, Sb, cls_b, Sb)
-                cls.index_copy_(0, sel, cls_b)
-                for t in (bi, bm, bs, cls_b, sel):
-                    t.record_stream(side)
-            used.append(side)
-        for side in used:
-            main.wait_stream(side)
+
+        def run(bi, bm, bs, Sb, _, outs_b, ws_key):
+            n = bi.shape[0]
+            m, ws, mb = self.be._workspace(ws_key, Sb, n, dev)
+            rc = _lib.load().capamd_parade_passage_cls(_ptr(bi), _ptr(bm), _ptr(bs), n, 1, Sb, ctypes.byref(m), mb, _ptr(ws), ws.numel(),
+                                                       _ptr(outs_b[0]), _ptr(status_word(dev).t), _stream())
+            _lib.check(rc, "capamd_parade_passage_cls")
+
+        self.be._by_length(fids, fmask, fseg, _shorter_lengths(S, skip_padding), run, outs=[(cls, 0)])
         return cls
 
     def head(self, cls, B, P, head_params, aggregated=False):
