@@ -15,6 +15,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CAPAMD_LIB_PATH") or os.path.join(_HERE, "csrc", "libcapreolus_amd.so")  # override: profiling builds only
 
+VERSION = 403  # CAPAMD_VERSION of include/capreolus_amd.h these signatures were written against
 OK, ERR_ARG, ERR_ALIGN, ERR_LAUNCH, ERR_WORKSPACE = 0, 1, 2, 3, 4
 LAUNCH_CONCURRENT = 1
 STATUS_DOC_ID_RANGE, STATUS_QUERY_ID_RANGE, STATUS_QUERY_OOV, STATUS_SCORE_NAN, STATUS_TIE_RANGE, STATUS_LIST_QUERY = 1, 2, 4, 8, 16, 32
@@ -109,6 +110,7 @@ SIGNATURES = {
     "capamd_bert_maxp_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _mp, _i, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "capamd_cedr_passage_features": (_i, [_vp, _vp, _vp, _i, _i, _i, _mp, _i64, _vp, _i64, _i, _vp, ctypes.POINTER(_i), _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "capamd_cedr_score": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "capamd_cedr_pool": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "capamd_parade_workspace_bytes": (_i64, [_hp, _i, _i]),
     "capamd_parade_passage_cls": (_i, [_vp, _vp, _vp, _i, _i, _i, _mp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "capamd_parade_head": (_i, [_vp, _i, _i, _hp, _vp, _i64, _vp, _vp, _vp]),
@@ -167,6 +169,8 @@ def load():
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype, fn.argtypes = res, args
+    if lib.capamd_version() != VERSION:
+        raise ImportError(f"{LIB_PATH} is C ABI {lib.capamd_version()}, this binding is written for {VERSION}: rebuild it (capreolus_amd/csrc/build.py)")
     _lib = lib
     return lib
 

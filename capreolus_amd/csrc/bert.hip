@@ -1256,6 +1256,27 @@ int capamd_cedr_passage_features(const int64_t* ids, const int64_t* mask, const 
   return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
 }
 
+/* the tap alone on a hidden state of the caller's making (exported for the unit tests): one selected "layer 0" through cedr_tap_layer */
+int capamd_cedr_pool(const void* x, int layout, const float* mr, const float* gamma, const float* beta, const int64_t* mask, const int64_t* seg,
+                     const float* query_mask0, int64_t p0, int64_t np, int64_t NP, int S, int hidden, int maxqlen, const float* mu,
+                     const float* sigma, int K, float* passage_kernel_sums, int dtype, void* stream) {
+  if (!x || !mask || !seg || !query_mask0 || !mu || !sigma || !passage_kernel_sums || (dtype != 0 && dtype != 1)) return CAPAMD_ERR_ARG;
+  if (layout < 0 || layout > 2 || hidden < 64 || hidden > 1024 || hidden % 64 || !supported_length(S)) return CAPAMD_ERR_ARG;
+  if (maxqlen < 1 || maxqlen + 1 > kCedrMaxA || maxqlen + 2 > S || K < 1 || K > kCedrMaxK) return CAPAMD_ERR_ARG;
+  if (p0 < 0 || np < 1 || p0 + np > NP) return CAPAMD_ERR_ARG;
+  const int A = maxqlen + 1;
+  if (layout == 0 ? (mr || cedr_pool_smem(S, A) > 160 * 1024) : (hidden % 256 != 0 || cedr_pool_cm_smem(S, hidden, A) > 160 * 1024)) return CAPAMD_ERR_ARG;
+  if (layout == 2 ? (!mr || !gamma || !beta) : mr != nullptr) return CAPAMD_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) != 0) return CAPAMD_ERR_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  (void)hipGetLastError();
+  const int layer0 = 0;
+  CedrTap tap{A, K, 1, &layer0, mu, sigma, query_mask0, passage_kernel_sums, nullptr, NP};
+  if (dtype == 1) cedr_tap_layer<_Float16>(tap, 0, (const _Float16*)x, mask, seg, p0, np, S, hidden, s, layout != 0, (const float2*)mr, gamma, beta);
+  else cedr_tap_layer<__bf16>(tap, 0, (const __bf16*)x, mask, seg, p0, np, S, hidden, s, layout != 0, (const float2*)mr, gamma, beta);
+  return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
+}
+
 int capamd_parade_passage_cls(const int64_t* ids, const int64_t* mask, const int64_t* seg, int B, int P, int S, const capamd_bert_model* m,
                               int64_t passages_per_microbatch, void* workspace, int64_t workspace_bytes, float* cls_rows, int* status,
                               void* stream) {

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CAPAMD_VERSION 402
+#define CAPAMD_VERSION 403
 
 #define CAPAMD_OK 0
 #define CAPAMD_ERR_ARG 1       /* null pointer / bad size / unsupported configuration */
@@ -365,6 +365,18 @@ int capamd_cedr_passage_features(const int64_t* ids, const int64_t* mask, const 
 int capamd_cedr_score(const float* passage_kernel_sums, const float* cls_rows, int B, int P, int maxqlen, int n_layers, int K, int hidden,
                       int cls_mode, const float* w1, const float* b1, int combine_hidden, const float* w2, const float* b2, float* out,
                       float* features_out, void* stream);
+/* The tap of capamd_cedr_passage_features alone, on one hidden state of the caller's making (exported for the unit tests; the same
+ * launch code as inside the encoder).  x, 16-bit (dtype 0 bf16, 1 fp16), 16-byte aligned (CAPAMD_ERR_ALIGN), by `layout`:
+ *   0  row-major hidden state [np*S][hidden]                                        (hidden % 64 == 0, 64..1024; mr NULL)
+ *   1  chunk-major (capamd_bert_gemm above), already normalised                     (hidden % 256 == 0; mr NULL)
+ *   2  chunk-major pre-LayerNorm sums; mr [np*S][2] = (mu, rstd) of every row, gamma / beta [hidden]: the hidden state is
+ *      fma((float(x) - mu) * rstd, gamma, beta) rounded to the 16-bit type, formed in registers
+ * mask, seg [np][S] are the micro-batch's own rows; query_mask0 [NP][maxqlen+1] and passage_kernel_sums [NP][K][maxqlen+1] are
+ * indexed by p0 + p, as in the encoder: rows p0 .. p0+np-1 are written, no other.  CAPAMD_ERR_ARG: S not a supported length,
+ * maxqlen + 1 > 32, maxqlen + 2 > S, K outside 1..11, p0 + np > NP, np < 1, a layout's conditions above, more than 160 KiB of LDS. */
+int capamd_cedr_pool(const void* x, int layout, const float* mr, const float* gamma, const float* beta, const int64_t* mask,
+                     const int64_t* seg, const float* query_mask0, int64_t p0, int64_t np, int64_t NP, int S, int hidden, int maxqlen,
+                     const float* mu, const float* sigma, int K, float* passage_kernel_sums, int dtype, void* stream);
 
 /* ---- PARADE (reference capreolus/reranker/ptparade.py, aggregation = "transformer") -----------------------------------------
  * Replaces PTParade_Class.forward (:66-78, called from PTParade.test).  Two calls:

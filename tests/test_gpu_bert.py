@@ -10,6 +10,7 @@ import torch
 from capreolus_amd import _lib, engine
 from capreolus_amd.reranker import PTBERTMaxP
 from oracle import bert_port
+from tests.cedr_case import from_cm as _from_cm, to_cm as _to_cm
 from tests.helpers import BERT_CASES, load_bert_case, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -54,16 +55,6 @@ def test_gemm_vs_torch(M, N, K, epi, dt):
     if epi == 4:
         ref = ref + resid.float()
     torch.testing.assert_close(out.float(), ref, rtol=rtol, atol=2e-2 if dt == "bf16" else 3e-3)  # one rounding of the result
-
-
-def _to_cm(x):
-    """row-major [M, C] -> the engine's chunk-major layout (include/capreolus_amd.h), flattened"""
-    M, C = x.shape
-    return x.reshape(M // 32, 32, C // 8, 8).permute(0, 2, 1, 3).contiguous().reshape(-1)
-
-
-def _from_cm(flat, M, C):
-    return flat.reshape(M // 32, C // 8, 32, 8).permute(0, 2, 1, 3).contiguous().reshape(M, C)
 
 
 @pytest.mark.parametrize("M,N,K,epi", [(512, 768, 768, 0), (256, 3072, 768, 1), (768, 256, 256, 0)])
