@@ -81,7 +81,7 @@ __device__ __forceinline__ int doc_n_one(const int32_t* dm, int t) { return dm[t
 #define CAPAMD_LISTS_COMPACT 1
 #endif
 constexpr bool kCompactRows = CAPAMD_LISTS_COMPACT != 0;
-struct ListQuery {
+struct alignas(16) ListQuery {      // (16: the KNRM pooling kernel reads a block's four ids as one int4; the workspace carves the array behind float4s)
   int id[kQT];             // query term ids (0: pad or beyond Q)
   float den[kQT];          // their rows' norms
 };

@@ -78,7 +78,10 @@ struct KnrmPoolArgs {
 // The sums add the same kernel values as the per-pair kernels in another order: equal to fp32 rounding of the sums (1e-6 relative).
 // Measured and not kept (profiles/r04/lists_pool_variants.txt, r05/lists_pool_*_ab.txt): the frequent terms' entries staged in LDS
 // (bank conflicts of 64 random ds_reads: 227 -> 281 us), eight documents per wave (261), a prefetch of the next pass's ids, 4 / 12 / 16
-// trips per pass.
+// trips per pass.  Round 7 (profiles/r07/lists_pool_pipeline_ab.txt): a two-deep pass pipeline (next pass's entries and the ids of the
+// pass after it in flight under the arithmetic: 88 VGPRs / 5 waves per SIMD against 64 / 8), the first pass's ids requested with the
+// metadata (94 / 5) and a per-trip skip of the exact-match kernel's zero v_exp_f32 (v_exp_f32 gives +0 from 2^-127 down on gfx950,
+// denormals flushed) - every one of them SLOWER, +4...+11 % of the serial step: the pass lives on its eight waves per SIMD.
 #ifndef CAPAMD_POOL_TRIPS
 #define CAPAMD_POOL_TRIPS 6       // 8 until round 6: 163 -> 158 us (5 the same, 7: 163, 3-4: 163-167, 12: 190; profiles/r06/lists_pool_ablation.txt)
 #endif
@@ -158,17 +161,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CAPAMD_POOL
   const int b = g.start[l] + doc;
   // what the mark pass left: the document's real terms, dense (int32), and its counts
   const int32_t* dm = a.meta + (int64_t)b * kDocMeta;
-  const DocWalk dw = doc_walk(a, b, dm);
-  const int n = dw.n, n_real_doc = dm[0];
+  DocWalk dw = doc_walk(a, b, dm);
+  int n = dw.n, n_real_doc = dm[0];
+  // The ids of the query's terms, a block's four in one 16-byte request, asked for TOGETHER with the document's counts: as a load per
+  // term behind its `< a.Q` test hipcc issued them one at a time, each waited for before the next - four trips to L2 in a row in front of
+  // every document's walk (the one statement below holds all the requests in front of the first wait).
+  static_assert(QP <= 2 && sizeof(ListQuery) % 16 == 0, "the pin below names two blocks; int4 reads of ListQuery::id");
+  int4 qid[QP];
+  {
+#pragma unroll
+    for (int h = 0; h < QP; ++h) qid[h] = *reinterpret_cast<const int4*>(a.qmeta[(int64_t)l * QP + h].id);
+    if (QP == 1) asm volatile("" : "+v"(n), "+v"(n_real_doc), "+v"(qid[0].x), "+v"(qid[0].y), "+v"(qid[0].z), "+v"(qid[0].w));
+    else asm volatile("" : "+v"(n), "+v"(n_real_doc), "+v"(qid[0].x), "+v"(qid[0].y), "+v"(qid[0].z), "+v"(qid[0].w), "+v"(qid[QP - 1].x), "+v"(qid[QP - 1].y),
+                      "+v"(qid[QP - 1].z), "+v"(qid[QP - 1].w));
+    n = __builtin_amdgcn_readfirstlane(n); n_real_doc = __builtin_amdgcn_readfirstlane(n_real_doc);
+    dw.n = n;
+  }
   const float* tabl = reinterpret_cast<const float*>(a.table + (int64_t)l * a.Vp * QP);
   float F = 0.f;
 #pragma unroll
   for (int h = 0; h < QP; ++h) {
     // the block's real query terms (wave-uniform): how many, and the first two
     int nq = 0, r0 = 0, r1 = 0;
+    const int qi[kQT] = {__builtin_amdgcn_readfirstlane(qid[h].x), __builtin_amdgcn_readfirstlane(qid[h].y), __builtin_amdgcn_readfirstlane(qid[h].z),
+                         __builtin_amdgcn_readfirstlane(qid[h].w)};
 #pragma unroll
     for (int tt = 0; tt < kQT; ++tt) {
-      const bool real = kQT * h + tt < a.Q && a.qmeta[(int64_t)l * QP + h].id[tt] > 0;
+      const bool real = kQT * h + tt < a.Q && qi[tt] > 0;
       r1 = (real && nq == 1) ? tt : r1;
       r0 = (real && nq == 0) ? tt : r0;
       nq += real ? 1 : 0;
