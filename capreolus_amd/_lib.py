@@ -15,7 +15,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CAPAMD_LIB_PATH") or os.path.join(_HERE, "csrc", "libcapreolus_amd.so")  # override: profiling builds only
 
-VERSION = 403  # CAPAMD_VERSION of include/capreolus_amd.h these signatures were written against
+VERSION = 404  # CAPAMD_VERSION of include/capreolus_amd.h these signatures were written against
 OK, ERR_ARG, ERR_ALIGN, ERR_LAUNCH, ERR_WORKSPACE = 0, 1, 2, 3, 4
 LAUNCH_CONCURRENT = 1
 STATUS_DOC_ID_RANGE, STATUS_QUERY_ID_RANGE, STATUS_QUERY_OOV, STATUS_SCORE_NAN, STATUS_TIE_RANGE, STATUS_LIST_QUERY = 1, 2, 4, 8, 16, 32
@@ -60,6 +60,18 @@ class TkModel(ctypes.Structure):
 
 
 _tp = ctypes.POINTER(TkModel)
+
+
+class HintModel(ctypes.Structure):
+    """capamd_hint_model (include/capreolus_amd.h)."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("emb", "ws_w", "ws_b")] + [
+        (f"{g}_{n}", ctypes.c_void_p) for g in ("gru1", "gru3") for n in ("wrz_w", "wrz_b", "w_w", "w_b", "u_w", "u_b")] + [
+        (n, ctypes.c_void_p) for n in ("lstm_w_ih", "lstm_w_hh", "lstm_b_ih", "lstm_b_hh", "lstm_w_ih_r", "lstm_w_hh_r", "lstm_b_ih_r", "lstm_b_hh_r",
+                                       "wv_w", "wv_b", "fc_w", "fc_b")] + [("vocab", ctypes.c_int64), ("dim", ctypes.c_int), ("kmax", ctypes.c_int)]
+
+
+_hnp = ctypes.POINTER(HintModel)
 
 # name -> (restype, argtypes); must list every symbol include/capreolus_amd.h declares
 SIGNATURES = {
@@ -116,6 +128,8 @@ SIGNATURES = {
     "capamd_parade_head": (_i, [_vp, _i, _i, _hp, _vp, _i64, _vp, _vp, _vp]),
     "capamd_tk_workspace_bytes": (_i64, [_tp, _i, _i, _i]),
     "capamd_tk_forward": (_i, [_vp, _vp, _i, _i, _i, _tp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "capamd_hint_workspace_bytes": (_i64, [_hnp, _i, _i, _i]),
+    "capamd_hint_forward": (_i, [_vp, _vp, _i, _i, _i, _hnp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "capamd_maxp_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "capamd_bert_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "capamd_bert_gemm_ln": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -1402,3 +1402,66 @@ class TKEngine:
         if check:
             st.raise_if_set()
         return (out, feats) if features else out
+
+
+HINT_WORKSPACE_BUDGET = 1 << 30    # bytes of window-transposed inputs per capamd_hint_forward call (documents run in micro-batches that fit)
+
+
+class HintEngine:
+    """HINT (reference HINT.py, HiNT_main.test_forward) through capamd_hint_forward.  Every parameter is read in place from the live
+    tensors (nn.Linear / nn.LSTM layout): there is nothing to re-lay out and so nothing cached but the workspace.
+    `docs_per_microbatch` (None: as many as HINT_WORKSPACE_BUDGET holds) bounds the workspace of a call."""
+
+    _FIELDS = (("emb", "HiNT1.embedding.weight"), ("ws_w", "HiNT1.Ws.weight"), ("ws_b", "HiNT1.Ws.bias")) + tuple(
+        (f"{g}_{f}_{k[0]}", f"HiNT1.{mod}.gru_cell.{lin}.{k}") for g, mod in (("gru1", "GRU2d1"), ("gru3", "GRU2d3"))
+        for f, lin in (("wrz", "Wrz"), ("w", "W"), ("u", "U")) for k in ("weight", "bias")) + tuple(
+        (f"lstm_{k[0]}_{k[1]}{'_r' if rev else ''}", f"HiNT1.lstm.{'weight' if k[0] == 'w' else 'bias'}_{k[1]}_l0{rev}")
+        for rev in ("", "_reverse") for k in (("w", "ih"), ("w", "hh"), ("b", "ih"), ("b", "hh"))) + (
+        ("wv_w", "HiNT1.Wv.weight"), ("wv_b", "HiNT1.Wv.bias"), ("fc_w", "HiNT1.fc.weight"), ("fc_b", "HiNT1.fc.bias"))
+
+    def __init__(self, docs_per_microbatch=None):
+        self.docs_per_microbatch = docs_per_microbatch
+        self._ws = None
+
+    def model(self, params, kmax):
+        """the capamd_hint_model of these live parameters (the second item keeps what it points to alive)"""
+        keep = {f: _f32(params[name].detach()) for f, name in self._FIELDS}
+        _need_gpu(*keep.values())
+        m = _lib.HintModel()
+        for f, t in keep.items():
+            setattr(m, f, t.data_ptr())
+        m.vocab, m.dim, m.kmax = keep["emb"].shape[0], keep["emb"].shape[1], int(kmax)
+        return m, keep
+
+    def forward(self, query, doc, params, kmax, evidence=False, check=True):
+        """int64 query ids [B, Q], document ids [B, L] -> fp32 scores [B] (and the [B, L // 100, 8] window evidence with evidence=True)"""
+        _need_gpu(query, doc)
+        q, d = _i64(query), _i64(doc)
+        B, Q = q.shape
+        L = d.shape[1]
+        if d.shape[0] != B:
+            raise ValueError(f"{B} query rows for {d.shape[0]} documents")
+        m, keep = self.model(params, kmax)
+        lib = _lib.load()
+        one = lib.capamd_hint_workspace_bytes(ctypes.byref(m), 1, Q, L)
+        if one < 0:
+            raise ValueError(f"unsupported HINT geometry: dim {m.dim}, kmax {m.kmax}, Q {Q}, L {L} "
+                             f"(dim <= 512, Q <= 32, 100 <= L, L // 100 <= 64, 1 <= kmax <= min(2 (L // 100), 32))")
+        nb = self.docs_per_microbatch
+        if nb is None:
+            per_doc = max(1, lib.capamd_hint_workspace_bytes(ctypes.byref(m), 2, Q, L) - one)
+            nb = max(1, HINT_WORKSPACE_BUDGET // per_doc)
+        nb = max(1, min(int(nb), max(B, 1)))
+        need = lib.capamd_hint_workspace_bytes(ctypes.byref(m), nb, Q, L)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != q.device:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        out = torch.empty(B, dtype=torch.float32, device=q.device)
+        ev = torch.empty((B, L // 100, 8), dtype=torch.float32, device=q.device) if evidence else None
+        st = status_word(q.device)
+        rc = lib.capamd_hint_forward(_ptr(q), _ptr(d), B, Q, L, ctypes.byref(m), nb, _ptr(self._ws), self._ws.numel(), _ptr(out), _ptr(ev),
+                                     _ptr(st.t), _stream())
+        _lib.check(rc, "capamd_hint_forward")
+        if check:
+            st.raise_if_set()
+        return (out, ev) if evidence else out

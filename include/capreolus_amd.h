@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CAPAMD_VERSION 403
+#define CAPAMD_VERSION 404
 
 #define CAPAMD_OK 0
 #define CAPAMD_ERR_ARG 1       /* null pointer / bad size / unsupported configuration */
@@ -445,6 +445,41 @@ typedef struct capamd_tk_model {
 int64_t capamd_tk_workspace_bytes(const capamd_tk_model* m, int docs_per_microbatch, int Q, int L);
 int capamd_tk_forward(const int64_t* q_ids, const int64_t* d_ids, int B, int Q, int L, const capamd_tk_model* m, int docs_per_microbatch,
                       void* workspace, int64_t workspace_bytes, float* out, float* features_out, int* status, void* stream);
+
+/* ---- HINT (reference capreolus/reranker/HINT.py, HiNT_main.test_forward -> HiNT.forward, called from HINT.test) -------------------
+ * score[b] of query ids q_ids [B, Q] against document ids d_ids [B, L] (int64), fp32 throughout.  P = L / 100 windows of 100 terms
+ * (the reference's hard-coded width); the terms behind P x 100 are not read.  Per window and query term i, document term j:
+ *   cos_ij = (q_i / (|q_i| + 1e-7)) . (d_j / (|d_j| + 1e-7));  xor_ij = 1 where the ids are equal (pad against pad included);
+ *   channels [Ws q_i + b, Ws d_j + b, M_ij], all three zeroed where BOTH ids are 0;
+ *   the spatial GRU (GRUCell2d, hidden 2) over the Q x 100 cells, query rows outside, its last cell's state: gru1 on the xor and the
+ *   cos tensor, gru3 on both with both axes reversed -> 8 values per window [H_xor, H_cos, H_xor_inv, H_cos_inv];
+ *   a bidirectional LSTM (hidden 6) over the P windows from zero state, forward + backward; tanh(Wv .); the 2P rows [vt; lstm]
+ *   top-kmax sorted per hidden unit, flattened unit * kmax + rank; fc.
+ * The parameters are read in place from the live fp32 tensors in nn.Linear / nn.LSTM layout: ws_w [dim], ws_b [1]; per GRU cell
+ * wrz_w [14][9], wrz_b [14], w_w [2][3], w_b [2], u_w [2][6], u_b [2]; lstm_w_ih [24][8], lstm_w_hh [24][6], lstm_b_ih / _b_hh [24]
+ * (gates i, f, g, o) and the *_r set of the reverse direction; wv_w [6][8], wv_b [6]; fc_w [6 kmax], fc_b [1].
+ * emb [vocab][dim] is read in place; ids outside [0, vocab) are scored as a zero row and set CAPAMD_STATUS_DOC_ID_RANGE /
+ * _QUERY_ID_RANGE (nn.Embedding raises).  Limits: 1 <= dim <= 512, 1 <= Q <= 32, 100 <= L, P <= 64, 1 <= kmax <= min(2 P, 32).
+ * Documents run in micro-batches of docs_per_microbatch; the workspace (256-byte aligned) is
+ * capamd_hint_workspace_bytes(m, docs_per_microbatch, Q, L) bytes (-1: unsupported geometry).  evidence_out (optional) [B][P][8]: the
+ * LSTM's input.  Each document's score is independent of the micro-batch size and of the other documents of the call, bit for bit. */
+typedef struct capamd_hint_gru {
+  const float *wrz_w, *wrz_b, *w_w, *w_b, *u_w, *u_b;
+} capamd_hint_gru;
+typedef struct capamd_hint_model {
+  const float* emb;                      /* [vocab][dim]    HiNT1.embedding.weight */
+  const float *ws_w, *ws_b;              /* HiNT1.Ws */
+  capamd_hint_gru gru1, gru3;            /* HiNT1.GRU2d1.gru_cell, HiNT1.GRU2d3.gru_cell */
+  const float *lstm_w_ih, *lstm_w_hh, *lstm_b_ih, *lstm_b_hh;           /* HiNT1.lstm.*_l0 */
+  const float *lstm_w_ih_r, *lstm_w_hh_r, *lstm_b_ih_r, *lstm_b_hh_r;   /* HiNT1.lstm.*_l0_reverse */
+  const float *wv_w, *wv_b, *fc_w, *fc_b;
+  int64_t vocab;
+  int dim, kmax;
+} capamd_hint_model;
+
+int64_t capamd_hint_workspace_bytes(const capamd_hint_model* m, int docs_per_microbatch, int Q, int L);
+int capamd_hint_forward(const int64_t* q_ids, const int64_t* d_ids, int B, int Q, int L, const capamd_hint_model* m, int docs_per_microbatch,
+                        void* workspace, int64_t workspace_bytes, float* out, float* evidence_out, int* status, void* stream);
 
 /* ---- ConvKNRM ------------------------------------------------------------------------
  * Replaces ConvKNRM_class.forward, capreolus/reranker/ConvKNRM.py:42-77 (called from ConvKNRM.test :112-116).
