@@ -15,10 +15,11 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CAPAMD_LIB_PATH") or os.path.join(_HERE, "csrc", "libcapreolus_amd.so")  # override: profiling builds only
 
-VERSION = 404  # CAPAMD_VERSION of include/capreolus_amd.h these signatures were written against
+VERSION = 405  # CAPAMD_VERSION of include/capreolus_amd.h these signatures were written against
 OK, ERR_ARG, ERR_ALIGN, ERR_LAUNCH, ERR_WORKSPACE = 0, 1, 2, 3, 4
 LAUNCH_CONCURRENT = 1
 STATUS_DOC_ID_RANGE, STATUS_QUERY_ID_RANGE, STATUS_QUERY_OOV, STATUS_SCORE_NAN, STATUS_TIE_RANGE, STATUS_LIST_QUERY = 1, 2, 4, 8, 16, 32
+STATUS_SHORT_DOC = 64
 
 _vp, _i, _i64, _sz, _u, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_uint, ctypes.c_float
 
@@ -72,6 +73,16 @@ class HintModel(ctypes.Structure):
 
 
 _hnp = ctypes.POINTER(HintModel)
+
+
+class PositModel(ctypes.Structure):
+    """capamd_posit_model (include/capreolus_amd.h)."""
+
+    _fields_ = [("emb", ctypes.c_void_p), ("w_ih", ctypes.c_void_p * 2), ("w_hh", ctypes.c_void_p * 2), ("bias", ctypes.c_void_p * 2)] + [
+        (n, ctypes.c_void_p) for n in ("q1_w", "q1_b", "wg_w", "wg_b")] + [("vocab", ctypes.c_int64), ("pad", ctypes.c_int64), ("dim", ctypes.c_int)]
+
+
+_pop = ctypes.POINTER(PositModel)
 
 # name -> (restype, argtypes); must list every symbol include/capreolus_amd.h declares
 SIGNATURES = {
@@ -130,6 +141,8 @@ SIGNATURES = {
     "capamd_tk_forward": (_i, [_vp, _vp, _i, _i, _i, _tp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "capamd_hint_workspace_bytes": (_i64, [_hnp, _i, _i, _i]),
     "capamd_hint_forward": (_i, [_vp, _vp, _i, _i, _i, _hnp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "capamd_posit_workspace_bytes": (_i64, [_pop, _i, _i, _i]),
+    "capamd_posit_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _pop, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "capamd_maxp_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "capamd_bert_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "capamd_bert_gemm_ln": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

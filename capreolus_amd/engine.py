@@ -68,6 +68,10 @@ class deferred_status:
         return False
 
 
+class IdRangeError(IndexError, ValueError):
+    """an id outside the embedding table: the IndexError nn.Embedding raises, and a ValueError as every other refused input is"""
+
+
 class StatusWord:
     """The device int32 the kernels OR data-dependent error bits into (include/capreolus_amd.h)."""
 
@@ -93,7 +97,10 @@ class StatusWord:
             if bits & (_lib.STATUS_SCORE_NAN | _lib.STATUS_TIE_RANGE):
                 raise ValueError("ranking: " + ("a score is NaN; " if bits & _lib.STATUS_SCORE_NAN else "") +
                                  ("a tie-break rank is outside 0..n-1" if bits & _lib.STATUS_TIE_RANGE else ""))
-            raise IndexError("index out of range in self: " + "; ".join(msgs))
+            if bits & _lib.STATUS_SHORT_DOC:
+                raise ValueError("POSITDRMM: a document has fewer than 2 non-pad terms (the reference's match statistics divide by its "
+                                 "length and by its number of bigrams)")
+            raise IdRangeError("index out of range in self: " + "; ".join(msgs))
 
 
 _status_words = {}
@@ -1465,3 +1472,113 @@ class HintEngine:
         if check:
             st.raise_if_set()
         return (out, ev) if evidence else out
+
+
+POSIT_WORKSPACE_BUDGET = 6 << 30    # bytes of activations per capamd_posit_forward call: 1000 pairs of 4 x 800 terms at dim 300 fit at once
+
+
+class PositEngine:
+    """POSITDRMM (reference POSITDRMM.py, POSITDRMM_class.test_forward) through capamd_posit_forward.  The LSTM's weights are packed
+    into the kernels' padded, gate-interleaved layout once per parameter version (include/capreolus_amd.h); the embedding table, Q1 and
+    Wg are read in place.  `docs_per_microbatch` (None: B in as few equal parts as POSIT_WORKSPACE_BUDGET allows) bounds the workspace."""
+
+    _LSTM = tuple(f"posit1.encoding_layer.{k}_l{n}{rev}" for n in (0, 1) for rev in ("", "_reverse")
+                  for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+
+    def __init__(self, docs_per_microbatch=None):
+        self.docs_per_microbatch = docs_per_microbatch
+        self._ws = None
+        self._key = None
+        self._keep = None
+
+    @staticmethod
+    def _pack(params, D):
+        """per layer (w_ih [2, 4 Dp, K], w_hh [2, 4 Dp, Dp], bias [2, 4 Dp]), zero-padded, gate rows reordered"""
+        Dp = (D + 63) // 64 * 64
+        dev = params[PositEngine._LSTM[0]].device
+        p = torch.arange(4 * Dp, device=dev)
+        unit, gate = (p // 64) * 16 + p % 16, (p % 64) // 16
+        dst = p[unit < D]
+        src = (gate * D + unit)[unit < D]
+        out = []
+        for n in (0, 1):
+            K = Dp * (n + 1)
+            w_ih = torch.zeros(2, 4 * Dp, K, dtype=torch.float32, device=dev)
+            w_hh = torch.zeros(2, 4 * Dp, Dp, dtype=torch.float32, device=dev)
+            bias = torch.zeros(2, 4 * Dp, dtype=torch.float32, device=dev)
+            for d, rev in enumerate(("", "_reverse")):
+                wi, wh, bi, bh = (_f32(params[f"posit1.encoding_layer.{k}_l{n}{rev}"].detach())
+                                  for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
+                for half in range(n + 1):                      # layer 1 reads [forward half, backward half], each in its own Dp columns
+                    w_ih[d, dst, half * Dp: half * Dp + D] = wi[src, half * D: (half + 1) * D]
+                w_hh[d, dst, :D] = wh[src]
+                bias[d, dst] = bi[src] + bh[src]
+            # W_hh fragment-major, [direction][unit block][k / 16][gate][lane = 16 (k % 16 // 4) + unit % 16][4]: a wave's load is contiguous
+            w_hh = w_hh.view(2, Dp // 16, 4, 16, Dp // 16, 4, 4).permute(0, 1, 4, 2, 5, 3, 6).contiguous()
+            out.append((w_ih, w_hh, bias))
+        return out
+
+    def model(self, params, pad):
+        """the capamd_posit_model of these live parameters (packing the LSTM again only when one of its parameters changed)"""
+        emb = _f32(params["posit1.embedding.weight"].detach())
+        heads = [_f32(params[k].detach()).reshape(-1) for k in ("posit1.Q1.weight", "posit1.Q1.bias", "posit1.Wg.weight", "posit1.Wg.bias")]
+        _need_gpu(emb, *heads, *(params[k] for k in self._LSTM))
+        key = tuple((params[k].data_ptr(), params[k]._version) for k in self._LSTM)
+        if key != self._key:
+            self._keep = self._pack(params, emb.shape[1])
+            self._key = key
+        m = _lib.PositModel()
+        m.emb = emb.data_ptr()
+        for n, (w_ih, w_hh, bias) in enumerate(self._keep):
+            m.w_ih[n], m.w_hh[n], m.bias[n] = w_ih.data_ptr(), w_hh.data_ptr(), bias.data_ptr()
+        m.q1_w, m.q1_b, m.wg_w, m.wg_b = (t.data_ptr() for t in heads)
+        m.vocab, m.pad, m.dim = emb.shape[0], int(pad), emb.shape[1]
+        return m, (emb, heads, self._keep)     # (the second item keeps what m points to alive)
+
+    def forward(self, query, query_idf, doc, params, pad, extras=None, bm25=None, details=False, check=True):
+        """int64 query ids [B, Q], fp32 idf [B, Q], document ids [B, L]; extras [B, 4], or bm25 [B] (the three match statistics are then
+        the kernel's own) -> fp32 scores [B]; with details=True also a dict of features [B, Q, 6], stats [B, 3], query_context
+        [B, Q, 2 dim] and doc_context [B, L, 2 dim]"""
+        _need_gpu(query, query_idf, doc, extras, bm25)
+        if (extras is None) == (bm25 is None):
+            raise ValueError("give either extras [B, 4] or bm25 [B]")
+        q, d, idf = _i64(query), _i64(doc), _f32(query_idf)
+        B, Q = q.shape
+        L = d.shape[1]
+        side = _f32(extras).reshape(-1) if extras is not None else _f32(bm25).reshape(-1)
+        if d.shape[0] != B or tuple(idf.shape) != (B, Q) or side.numel() != (4 * B if extras is not None else B):
+            raise ValueError(f"{B} query rows of {Q} terms for {d.shape[0]} documents, idf {tuple(idf.shape)}, {side.numel()} extra values")
+        m, keep = self.model(params, pad)
+        lib = _lib.load()
+        one = lib.capamd_posit_workspace_bytes(ctypes.byref(m), 1, Q, L)
+        if one < 0:
+            raise ValueError(f"unsupported POSITDRMM geometry: dim {m.dim}, Q {Q}, L {L} (dim <= 320, Q <= 16, 5 <= L <= 8192)")
+        nb = self.docs_per_microbatch
+        if nb is None:
+            # (between large micro-batches, where the projection chunk has reached its fixed size: what a pair adds)
+            per_doc = max(1, (lib.capamd_posit_workspace_bytes(ctypes.byref(m), 1 << 16, Q, L) - lib.capamd_posit_workspace_bytes(ctypes.byref(m), 1 << 15, Q, L)) >> 15)
+            most = max(1, (POSIT_WORKSPACE_BUDGET - (512 << 20)) // per_doc)
+            parts = -(-max(B, 1) // most)
+            nb = -(-max(B, 1) // parts)
+        nb = max(1, min(int(nb), max(B, 1)))
+        need = lib.capamd_posit_workspace_bytes(ctypes.byref(m), nb, Q, L)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != q.device:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        out = torch.empty(B, dtype=torch.float32, device=q.device)
+        det = None
+        if details:
+            D = m.dim
+            det = {"features": torch.empty((B, Q, 6), dtype=torch.float32, device=q.device),
+                   "stats": torch.empty((B, 3), dtype=torch.float32, device=q.device),
+                   "query_context": torch.empty((B, Q, 2 * D), dtype=torch.float32, device=q.device),
+                   "doc_context": torch.empty((B, L, 2 * D), dtype=torch.float32, device=q.device)}
+        st = status_word(q.device)
+        rc = lib.capamd_posit_forward(_ptr(q), _ptr(idf), _ptr(d), _ptr(side) if extras is not None else None, _ptr(side) if extras is None else None,
+                                      B, Q, L, ctypes.byref(m), nb, _ptr(self._ws), self._ws.numel(), _ptr(out),
+                                      *((_ptr(det[k]) for k in ("features", "stats", "query_context", "doc_context")) if details else (None,) * 4),
+                                      _ptr(st.t), _stream())
+        _lib.check(rc, "capamd_posit_forward")
+        if check:
+            st.raise_if_set()
+        return (out, det) if details else out

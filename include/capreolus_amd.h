@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CAPAMD_VERSION 404
+#define CAPAMD_VERSION 405
 
 #define CAPAMD_OK 0
 #define CAPAMD_ERR_ARG 1       /* null pointer / bad size / unsupported configuration */
@@ -45,6 +45,7 @@ extern "C" {
 #define CAPAMD_STATUS_TIE_RANGE 16     /* capamd_ndcg_cut: a tie-break rank outside 0..n-1 */
 #define CAPAMD_STATUS_LIST_QUERY 32    /* *_forward_lists: a pair of a list brings another query row (DRMM, DRMM-TKS: or another idf row) than
                                           the list's first pair - a list is ONE query against its documents */
+#define CAPAMD_STATUS_SHORT_DOC 64     /* capamd_posit_forward: a document of fewer than 2 non-pad terms (the reference divides by zero) */
 
 /* library identity */
 int capamd_version(void);
@@ -480,6 +481,45 @@ typedef struct capamd_hint_model {
 int64_t capamd_hint_workspace_bytes(const capamd_hint_model* m, int docs_per_microbatch, int Q, int L);
 int capamd_hint_forward(const int64_t* q_ids, const int64_t* d_ids, int B, int Q, int L, const capamd_hint_model* m, int docs_per_microbatch,
                         void* workspace, int64_t workspace_bytes, float* out, float* evidence_out, int* status, void* stream);
+
+/* ---- POSITDRMM (reference capreolus/reranker/POSITDRMM.py, POSITDRMM_class.test_forward -> POSITDRMM_basic.forward) ---------------
+ * score[b] of query ids q_ids [B, Q] (idf q_idf [B, Q] fp32) against document ids d_ids [B, L] (int64), fp32 throughout:
+ *   M_cos_ij = (q_i / (|q_i| + 1e-7)) . (d_j / (|d_j| + 1e-7));  xor_ij = 1 where the ids are equal and q_i != pad;
+ *   the 2-layer bidirectional LSTM (hidden = dim, gates i, f, g, o, no dropout) from zero state over the Q query positions and over
+ *   ALL L document positions, pads included; context rows [fwd + x, bwd + x]; M_ctx_ij = their cosine, no epsilon;
+ *   per query term the max and the mean of the 5 largest over j of M_cos, M_ctx, xor -> 6 features; LeakyReLU(0.01)(Q1 .);
+ *   ans = sum_i softmax(q_idf)_i . ;  score = Wg [ans, extras(4)].
+ * extras [B][4], or NULL: then [s0, s1, s2, bm25[b]] with the reference's get_exact_match_stats computed here from the ids (the query
+ * as it is, the document without its pads; len = its non-pad terms): s0 = matches / len, s1 = sum_i (matches of q_i) idf_i / len
+ * (summed in query order in fp32), s2 = matches of query bigrams among the cleaned document's bigrams / (len - 1).  They are always
+ * computed; len < 2 sets CAPAMD_STATUS_SHORT_DOC (the three are then 0).
+ * Weights in the padded layout (built once per set of weights by the caller; every pad element 0, 16-byte aligned), Dp =
+ * roundup(dim, 64), both directions back to back (forward, reverse), gate rows reordered: packed row ub 64 + g 16 + j = row g dim + u
+ * of the nn.LSTM tensor (g = 0..3: i, f, g, o; u = ub 16 + j < dim);
+ *   w_ih[0] [2][4 Dp][Dp]; w_ih[1] [2][4 Dp][2 Dp] with the input columns dim .. 2 dim - 1 at Dp ..; bias[l] [2][4 Dp] = bias_ih + bias_hh;
+ *   w_hh[l] [2][4 Dp x Dp], its packed rows stored fragment-major for the recurrence's MFMA loads: [ub][k / 16][g][lane 0..63][4] holds
+ *   packed row ub 64 + g 16 + (lane & 15), columns 16 (k / 16) + 4 (lane >> 4) .. + 3.
+ * emb [vocab][dim], q1_w [6], q1_b [1], wg_w [5], wg_b [1] are read in place; ids outside [0, vocab) are scored as a zero row and set
+ * CAPAMD_STATUS_DOC_ID_RANGE / _QUERY_ID_RANGE.  Limits: 1 <= dim <= 320, 1 <= Q <= 16, 5 <= L <= 8192, docs_per_microbatch <= 2^20.
+ * Pairs run in micro-batches of docs_per_microbatch; the workspace (256-byte aligned) is capamd_posit_workspace_bytes(m,
+ * docs_per_microbatch, Q, L) bytes (-1: unsupported geometry; about 16 Dp (L + Q) + 8 Q L bytes per pair plus 512 MiB of input
+ * projections).  Optional outputs: features_out [B][Q][6] (the input of Q1), stats_out [B][3], qctx_out [B][Q][2 dim], dctx_out
+ * [B][L][2 dim] (the context rows).  Each pair's results are independent of the micro-batch size and of the other pairs of the call,
+ * bit for bit. */
+typedef struct capamd_posit_model {
+  const float* emb;                      /* [vocab][dim]    posit1.embedding.weight */
+  const float* w_ih[2];                  /* per layer, packed (above) */
+  const float* w_hh[2];
+  const float* bias[2];
+  const float *q1_w, *q1_b, *wg_w, *wg_b;   /* posit1.Q1, posit1.Wg */
+  int64_t vocab, pad;
+  int dim;
+} capamd_posit_model;
+
+int64_t capamd_posit_workspace_bytes(const capamd_posit_model* m, int docs_per_microbatch, int Q, int L);
+int capamd_posit_forward(const int64_t* q_ids, const float* q_idf, const int64_t* d_ids, const float* extras, const float* bm25, int B, int Q, int L,
+                         const capamd_posit_model* m, int docs_per_microbatch, void* workspace, int64_t workspace_bytes, float* out,
+                         float* features_out, float* stats_out, float* qctx_out, float* dctx_out, int* status, void* stream);
 
 /* ---- ConvKNRM ------------------------------------------------------------------------
  * Replaces ConvKNRM_class.forward, capreolus/reranker/ConvKNRM.py:42-77 (called from ConvKNRM.test :112-116).
