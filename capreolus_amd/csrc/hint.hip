@@ -15,9 +15,9 @@
 //                  forward + backward, tanh(Wv .), the sorted top-kmax of the 2P values per hidden unit (by rank counting), fc.
 // Each document's result is independent of the other documents and of the micro-batch size, bit for bit.
 #include "capreolus_amd.h"
-#include <hip/hip_runtime.h>
+#include "cos_front.h"
+#include "workspace.h"
 #include <math.h>
-#include <stdint.h>
 
 namespace {
 
@@ -27,26 +27,15 @@ constexpr int kMaxQ = 32, kMaxP = 64, kMaxDim = 512, kMaxK = 32, kH = 6, kEv = 8
 struct Ws {
   float *Y, *cos, *X, *ev;
   uint32_t *eq, *mk;
+  size_t bytes;
 };
 
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
-
-size_t ws_layout(int64_t nb, int Q, int P, char* base, Ws* w) {
+// the window-transposed inputs of the GRU for nb documents, and its evidence
+Ws carve(int64_t nb, int Q, int P, void* base) {
   const int64_t NW = nb * P;
-  const size_t sizes[6] = {(size_t)(kWin * NW), (size_t)(kWin * NW) * Q, (size_t)(nb * Q), (size_t)(NW * kEv), (size_t)(kWin * NW), (size_t)(kWin * NW)};
-  void** ptrs[6] = {(void**)&w->Y, (void**)&w->cos, (void**)&w->X, (void**)&w->ev, (void**)&w->eq, (void**)&w->mk};
-  size_t off = 0;
-  for (int i = 0; i < 6; ++i) {
-    if (base) *ptrs[i] = base + off;
-    off += up256(sizes[i] * 4);
-  }
-  return off;
-}
-
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  Carver c(base);
+  return {c.take(kWin * NW), c.take((size_t)(kWin * NW) * Q), c.take(nb * Q), c.take(NW * kEv), c.take<uint32_t>(kWin * NW), c.take<uint32_t>(kWin * NW),
+          c.bytes()};
 }
 
 // One pass of a 16-lane group over a document term's row e against the query rows i0 .. i0 + 3 (normalised, in LDS): their cosines to
@@ -95,8 +84,8 @@ __global__ __launch_bounds__(256) void front_kernel(const int64_t* __restrict__ 
                                                     const float* __restrict__ ws_b, int64_t NW, float* __restrict__ Yt, float* __restrict__ cost,
                                                     uint32_t* __restrict__ eqt, uint32_t* __restrict__ mkt, float* __restrict__ X, int* status) {
   extern __shared__ float lds[];
-  float* qn = lds;                                                  // [Q][D]
-  int64_t* qid = reinterpret_cast<int64_t*>(lds + (size_t)((Q * D + 1) / 2 * 2));   // [Q] (8-byte aligned)
+  float* qn = lds;                                                           // [Q][D]
+  int64_t* qid = reinterpret_cast<int64_t*>(lds + FrontLds(Q, D, 0).qid);    // [Q]
   const int tid = threadIdx.x, g = tid >> 4, l = tid & 15;
   const int64_t b = blockIdx.x;
   const float bias = ws_b[0];
@@ -147,8 +136,6 @@ __global__ __launch_bounds__(256) void front_kernel(const int64_t* __restrict__ 
 struct GruPtrs {
   const float *wrz_w, *wrz_b, *w_w, *w_b, *u_w, *u_b;
 };
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // softmax over the four gates of one hidden unit, as F.softmax does (max subtracted)
 __device__ __forceinline__ void softmax4(float& a, float& b, float& c, float& d) {
@@ -348,8 +335,7 @@ extern "C" {
 
 int64_t capamd_hint_workspace_bytes(const capamd_hint_model* m, int docs_per_microbatch, int Q, int L) {
   if (!shape_ok(m, Q, L) || docs_per_microbatch < 1) return -1;
-  Ws w;
-  return (int64_t)ws_layout(docs_per_microbatch, Q, L / kWin, nullptr, &w);
+  return (int64_t)carve(docs_per_microbatch, Q, L / kWin, nullptr).bytes;
 }
 
 int capamd_hint_forward(const int64_t* q_ids, const int64_t* d_ids, int B, int Q, int L, const capamd_hint_model* m, int docs_per_microbatch,
@@ -366,34 +352,28 @@ int capamd_hint_forward(const int64_t* q_ids, const int64_t* d_ids, int B, int Q
   const int P = L / kWin;
   const int64_t nb = docs_per_microbatch < B ? docs_per_microbatch : B;
   if (nb * P * (int64_t)kWin * Q > (int64_t)1 << 40) return CAPAMD_ERR_ARG;
-  Ws w;
-  if ((int64_t)ws_layout(nb, Q, P, nullptr, &w) > workspace_bytes) return CAPAMD_ERR_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return CAPAMD_ERR_ALIGN;
-  ws_layout(nb, Q, P, (char*)workspace, &w);
-  hipStream_t s = (hipStream_t)stream;
-  (void)hipGetLastError();
-  const size_t front_lds = (size_t)((Q * m->dim + 1) / 2 * 2) * 4 + (size_t)Q * 8;
-  // (only Q = 32 with dim = 512, the two limits together, passes the 64 KiB a kernel gets without asking: 64 KiB + 256 bytes)
-  if (front_lds > 64 * 1024 &&
-      hipFuncSetAttribute(reinterpret_cast<const void*>(front_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)front_lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return CAPAMD_ERR_LAUNCH;
-  }
+  const size_t front_lds = FrontLds(Q, m->dim, 0).bytes;
   const GruPtrs g1 = {m->gru1.wrz_w, m->gru1.wrz_b, m->gru1.w_w, m->gru1.w_b, m->gru1.u_w, m->gru1.u_b};
   const GruPtrs g3 = {m->gru3.wrz_w, m->gru3.wrz_b, m->gru3.w_w, m->gru3.w_b, m->gru3.u_w, m->gru3.u_b};
   const HeadPtrs hp = {{m->lstm_w_ih, m->lstm_w_ih_r}, {m->lstm_w_hh, m->lstm_w_hh_r}, {m->lstm_b_ih, m->lstm_b_ih_r}, {m->lstm_b_hh, m->lstm_b_hh_r},
                        m->wv_w, m->wv_b, m->fc_w, m->fc_b};
-  for (int64_t b0 = 0; b0 < B; b0 += nb) {
-    const int64_t n = (B - b0) < nb ? (B - b0) : nb;
-    const int64_t NW = n * P;
-    hipLaunchKernelGGL(front_kernel, dim3((unsigned)n), dim3(256), front_lds, s, q_ids + b0 * Q, d_ids + b0 * L, Q, L, P, m->emb, m->vocab, m->dim,
-                       m->ws_w, m->ws_b, NW, w.Y, w.cos, w.eq, w.mk, w.X, status);
-    hipLaunchKernelGGL(gru_kernel, dim3((unsigned)((2 * NW + 63) / 64), 2), dim3(64), (size_t)Q * 64 * 12 + 140 * 4, s, g1, g3, w.Y, w.cos, w.eq, w.mk, w.X, Q, P,
-                       NW, w.ev);
-    hipLaunchKernelGGL(head_kernel, dim3((unsigned)n), dim3(64), 0, s, hp, w.ev, P, m->kmax, out + b0,
-                       evidence_out ? evidence_out + b0 * P * kEv : nullptr);
-  }
-  return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
+  hipStream_t s = (hipStream_t)stream;
+  return run_microbatches(
+      B, docs_per_microbatch, workspace, workspace_bytes, [&](int64_t n, void* base) { return carve(n, Q, P, base); },
+      [&](int64_t b0, int64_t n, const Ws& w) {
+        // (only Q = 32 with dim = 512, the two limits together, passes the 64 KiB a kernel gets without asking: 64 KiB + 256 bytes)
+        if (b0 == 0 && front_lds > 64 * 1024 &&
+            hipFuncSetAttribute(reinterpret_cast<const void*>(front_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)front_lds) != hipSuccess)
+          return CAPAMD_ERR_LAUNCH;
+        const int64_t NW = n * P;
+        hipLaunchKernelGGL(front_kernel, dim3((unsigned)n), dim3(256), front_lds, s, q_ids + b0 * Q, d_ids + b0 * L, Q, L, P, m->emb, m->vocab, m->dim,
+                           m->ws_w, m->ws_b, NW, w.Y, w.cos, w.eq, w.mk, w.X, status);
+        hipLaunchKernelGGL(gru_kernel, dim3((unsigned)((2 * NW + 63) / 64), 2), dim3(64), (size_t)Q * 64 * 12 + 140 * 4, s, g1, g3, w.Y, w.cos, w.eq, w.mk,
+                           w.X, Q, P, NW, w.ev);
+        hipLaunchKernelGGL(head_kernel, dim3((unsigned)n), dim3(64), 0, s, hp, w.ev, P, m->kmax, out + b0,
+                           evidence_out ? evidence_out + b0 * P * kEv : nullptr);
+        return CAPAMD_OK;
+      });
 }
 
 }  // extern "C"

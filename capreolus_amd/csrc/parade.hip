@@ -10,8 +10,7 @@
 //             -> LayerNorm + linear (the score)
 // Layer 2's output is read at row 0 only: its K and V need every row, its Q / attention / projections / FFN only row 0 (exact).
 #include "capreolus_amd.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "workspace.h"
 
 namespace {
 
@@ -190,10 +189,16 @@ bool geometry_ok(const capamd_parade_head_model* hm, int B, int P) {
          B >= 0 && P >= 1 && P + 1 <= kMaxRows;
 }
 
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
+struct Ws {
+  float *x0, *q, *k, *v, *ctx, *t, *xa, *x1, *mid;
+  size_t bytes;
+};
 
 // workspace: x0, q, k, v, ctx, t, xa, x1 ([M, H] each) and mid [M, F], M = B (P + 1)
-size_t ws_bytes(int64_t M, int H, int F) { return 8 * up256((size_t)M * H * 4) + up256((size_t)M * F * 4); }
+Ws carve(int64_t M, int H, int F, void* base) {
+  Carver c(base);
+  return {c.take(M * H), c.take(M * H), c.take(M * H), c.take(M * H), c.take(M * H), c.take(M * H), c.take(M * H), c.take(M * H), c.take(M * F), c.bytes()};
+}
 
 template <int EPI>
 void gemm(const float* A, int64_t lda, int M, int N, int K, GemmJobs jobs, int nz, const float* resid, int64_t ldr, hipStream_t s) {
@@ -207,15 +212,13 @@ GemmJobs one(const float* W, const float* bias, float* out) {
   return j;
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 int64_t capamd_parade_workspace_bytes(const capamd_parade_head_model* hm, int B, int P) {
   if (!geometry_ok(hm, B, P)) return -1;
-  return (int64_t)ws_bytes((int64_t)B * (P + 1), hm->hidden, hm->ffn);
+  return (int64_t)carve((int64_t)B * (P + 1), hm->hidden, hm->ffn, nullptr).bytes;
 }
 
 int capamd_parade_head(const float* cls_rows, int B, int P, const capamd_parade_head_model* hm, void* workspace, int64_t workspace_bytes,
@@ -228,17 +231,14 @@ int capamd_parade_head(const float* cls_rows, int B, int P, const capamd_parade_
   const int H = hm->hidden, F = hm->ffn, R = P + 1, heads = hm->heads;
   const int64_t M = (int64_t)B * R;
   if (M > (1 << 30)) return CAPAMD_ERR_ARG;
-  if ((int64_t)ws_bytes(M, H, F) > workspace_bytes) return CAPAMD_ERR_WORKSPACE;
+  if ((int64_t)carve(M, H, F, nullptr).bytes > workspace_bytes) return CAPAMD_ERR_WORKSPACE;
   // the GEMMs load 16 bytes at a time from the activations and the weight rows
   if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0 || !aligned16(cls_rows)) return CAPAMD_ERR_ALIGN;
   for (int i = 0; i < 16; i += 2)
     if (!aligned16(hm->layer1[i]) || !aligned16(hm->layer2[i])) return CAPAMD_ERR_ALIGN;
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();
-  char* p = (char*)workspace;
-  auto take = [&](size_t n) { float* r = (float*)p; p += up256(n * 4); return r; };
-  float *x0 = take(M * H), *q = take(M * H), *k = take(M * H), *v = take(M * H), *ctx = take(M * H), *t = take(M * H), *xa = take(M * H),
-        *x1 = take(M * H), *mid = take(M * F);
+  const auto [x0, q, k, v, ctx, t, xa, x1, mid, carved] = carve(M, H, F, workspace);
   const float eps = hm->ln_eps;
   const int Mi = (int)M;
 

@@ -22,7 +22,9 @@
 //                  Q1, LeakyReLU, softmax(idf), Wg over [ans, extras].
 // A pair's results do not depend on its tile mates, on the micro-batch size or on the chunk length, bit for bit.
 #include "capreolus_amd.h"
+#include "cos_front.h"
 #include "tk_gemm.h"
+#include "workspace.h"
 #include <math.h>
 
 namespace {
@@ -30,11 +32,10 @@ namespace {
 constexpr int kMaxQ = 16, kMaxDim = 320, kMaxL = 8192, kSeqTile = 16;
 constexpr int64_t kProjBytes = (int64_t)512 << 20;     // the two directions' projection buffers of one chunk
 
-int up64(int n) { return (n + 63) / 64 * 64; }
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
-
 struct Ws {
   float *X, *QX, *Y0, *Y1, *QY1, *P, *cst, *mcos, *mctx, *stats;
+  int T;          // positions per chunk of the recurrence: what P is sized for
+  size_t bytes;
 };
 
 int chunk_steps(int64_t nb, int Dp, int Q, int L) {
@@ -42,24 +43,12 @@ int chunk_steps(int64_t nb, int Dp, int Q, int L) {
   return (int)(t < 1 ? 1 : t > S ? S : t);
 }
 
-size_t ws_layout(int64_t nb, int Dp, int Q, int L, char* base, Ws* w) {
+Ws carve(int64_t nb, int Dp, int Q, int L, void* base) {
   const int64_t S = L > Q ? L : Q, T = chunk_steps(nb, Dp, Q, L);
-  const size_t sizes[10] = {(size_t)(L * nb * Dp),     (size_t)(Q * nb * Dp),     (size_t)(S * nb * 2 * Dp), (size_t)(L * nb * 2 * Dp),
-                            (size_t)(Q * nb * 2 * Dp), (size_t)(T * nb * 8 * Dp), (size_t)(2 * nb * Dp),     (size_t)(nb * Q * L),
-                            (size_t)(nb * Q * L),      (size_t)(nb * 4)};
-  float** ptrs[10] = {&w->X, &w->QX, &w->Y0, &w->Y1, &w->QY1, &w->P, &w->cst, &w->mcos, &w->mctx, &w->stats};
-  size_t off = 0;
-  for (int i = 0; i < 10; ++i) {
-    if (base) *ptrs[i] = reinterpret_cast<float*>(base + off);
-    off += up256(sizes[i] * 4);
-  }
-  return off;
-}
-
-__device__ __forceinline__ float group16_sum(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+  Carver c(base);
+  return {c.take(L * nb * Dp),     c.take(Q * nb * Dp), c.take(S * nb * 2 * Dp), c.take(L * nb * 2 * Dp), c.take(Q * nb * 2 * Dp),
+          c.take(T * nb * 8 * Dp), c.take(2 * nb * Dp), c.take(nb * Q * L),      c.take(nb * Q * L),      c.take(nb * 4),
+          (int)T,                  c.bytes()};
 }
 
 // One pass of a 16-lane group over a row val(0 .. W - 1) against the rows i0 .. i0 + 3 of qn [Q][W] (normalised, in LDS): the dot
@@ -100,9 +89,10 @@ __global__ __launch_bounds__(256) void front_kernel(const int64_t* __restrict__ 
                                                     float* __restrict__ X, float* __restrict__ QX, float* __restrict__ mcos,
                                                     float* __restrict__ stats, int* status) {
   extern __shared__ float lds[];
-  float* qn = lds;                                                                  // [Q][D]
-  int64_t* qid = reinterpret_cast<int64_t*>(lds + (size_t)((Q * D + 1) / 2 * 2));   // [Q] (8-byte aligned)
-  int* cnt = reinterpret_cast<int*>(qid + Q);                                       // [Q] matches per query term, [1] bigrams, [1] length
+  const FrontLds at(Q, D, Q + 2);
+  float* qn = lds;                                          // [Q][D]
+  int64_t* qid = reinterpret_cast<int64_t*>(lds + at.qid);  // [Q]
+  int* cnt = reinterpret_cast<int*>(lds + at.cnt);          // [Q] matches per query term, [1] bigrams, [1] length
   const int tid = threadIdx.x, g = tid >> 4, l = tid & 15;
   const int64_t b = blockIdx.x;
   if (tid < Q + 2) cnt[tid] = 0;
@@ -179,8 +169,6 @@ __global__ __launch_bounds__(256) void front_kernel(const int64_t* __restrict__ 
 }
 
 // ---- stage 2 ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 // Steps s0 .. s0 + Tc - 1 of one layer's recurrence for 16 sequences of one direction.  P [2][Tc n][4 Dp]: the chunk's input
 // projections with both biases, rows in ascending position; Y [S][n][2 Dp]; cst [2][n][Dp].  Packed gate order: row
 // ub 64 + gate 16 + j = gate (i, f, g, o) of hidden unit ub 16 + j.  Wave w owns the unit blocks w NB .. w NB + NB - 1; in the MFMA's
@@ -428,7 +416,8 @@ void launch_rec(int NB, unsigned grid, hipStream_t s, const float* P, const floa
 }
 
 // the two LSTM layers over n sequences of S positions: X [S][n][Dp] -> Yout [S][n][2 Dp] (forward half, backward half)
-void encode(const capamd_posit_model* m, int Dp, int n, int S, int T, const Ws& w, const float* X, float* Yout, hipStream_t s) {
+void encode(const capamd_posit_model* m, int Dp, int n, int S, const Ws& w, const float* X, float* Yout, hipStream_t s) {
+  const int T = w.T;
   const unsigned grid = 2u * (unsigned)((n + kSeqTile - 1) / kSeqTile);
   for (int layer = 0; layer < 2; ++layer) {
     const float* A = layer ? w.Y0 : X;
@@ -444,16 +433,13 @@ void encode(const capamd_posit_model* m, int Dp, int n, int S, int T, const Ws& 
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
 
 int64_t capamd_posit_workspace_bytes(const capamd_posit_model* m, int docs_per_microbatch, int Q, int L) {
   if (!shape_ok(m, Q, L) || docs_per_microbatch < 1 || docs_per_microbatch > (1 << 20)) return -1;
-  Ws w;
-  return (int64_t)ws_layout(docs_per_microbatch, up64(m->dim), Q, L, nullptr, &w);
+  return (int64_t)carve(docs_per_microbatch, up64(m->dim), Q, L, nullptr).bytes;
 }
 
 int capamd_posit_forward(const int64_t* q_ids, const float* q_idf, const int64_t* d_ids, const float* extras, const float* bm25, int B, int Q, int L,
@@ -468,32 +454,27 @@ int capamd_posit_forward(const int64_t* q_ids, const float* q_idf, const int64_t
     if (!aligned16(m->w_ih[i]) || !aligned16(m->w_hh[i])) return CAPAMD_ERR_ALIGN;
   }
   if (B == 0) return CAPAMD_OK;
-  const int64_t nb = docs_per_microbatch < B ? docs_per_microbatch : B;
   const int D = m->dim, Dp = up64(D);
-  Ws w;
-  if ((int64_t)ws_layout(nb, Dp, Q, L, nullptr, &w) > workspace_bytes) return CAPAMD_ERR_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return CAPAMD_ERR_ALIGN;
-  ws_layout(nb, Dp, Q, L, (char*)workspace, &w);
-  const int T = chunk_steps(nb, Dp, Q, L);
-  hipStream_t s = (hipStream_t)stream;
-  (void)hipGetLastError();
-  const size_t front_lds = (size_t)((Q * D + 1) / 2 * 2) * 4 + (size_t)Q * 8 + (size_t)(Q + 2) * 4;
+  const size_t front_lds = FrontLds(Q, D, Q + 2).bytes;
   const size_t pool_lds = (size_t)Q * 2 * D * 4 + (size_t)Q * 6 * 4;
-  for (int64_t b0 = 0; b0 < B; b0 += nb) {
-    const int n = (int)((B - b0) < nb ? (B - b0) : nb);
-    const int64_t* q = q_ids + b0 * Q;
-    const int64_t* d = d_ids + b0 * L;
-    const float* idf = q_idf + b0 * Q;
-    hipLaunchKernelGGL(front_kernel, dim3((unsigned)n), dim3(256), front_lds, s, q, idf, d, Q, L, m->emb, m->vocab, D, Dp, m->pad, (int64_t)n, w.X, w.QX,
-                       w.mcos, w.stats, status);
-    encode(m, Dp, n, Q, T, w, w.QX, w.QY1, s);
-    encode(m, Dp, n, L, T, w, w.X, w.Y1, s);
-    hipLaunchKernelGGL(pool_kernel, dim3((unsigned)n), dim3(256), pool_lds, s, q, idf, d, Q, L, D, Dp, m->pad, (int64_t)n, w.X, w.QX, w.Y1, w.QY1, w.mcos,
-                       w.mctx, w.stats, extras ? extras + b0 * 4 : nullptr, bm25 ? bm25 + b0 : nullptr, m->q1_w, m->q1_b, m->wg_w, m->wg_b, out + b0,
-                       features_out ? features_out + b0 * Q * 6 : nullptr, stats_out ? stats_out + b0 * 3 : nullptr,
-                       qctx_out ? qctx_out + b0 * Q * 2 * D : nullptr, dctx_out ? dctx_out + b0 * (int64_t)L * 2 * D : nullptr);
-  }
-  return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
+  hipStream_t s = (hipStream_t)stream;
+  return run_microbatches(
+      B, docs_per_microbatch, workspace, workspace_bytes, [&](int64_t nb, void* base) { return carve(nb, Dp, Q, L, base); },
+      [&](int64_t b0, int64_t nn, const Ws& w) {
+        const int n = (int)nn;
+        const int64_t* q = q_ids + b0 * Q;
+        const int64_t* d = d_ids + b0 * L;
+        const float* idf = q_idf + b0 * Q;
+        hipLaunchKernelGGL(front_kernel, dim3((unsigned)n), dim3(256), front_lds, s, q, idf, d, Q, L, m->emb, m->vocab, D, Dp, m->pad, (int64_t)n, w.X,
+                           w.QX, w.mcos, w.stats, status);
+        encode(m, Dp, n, Q, w, w.QX, w.QY1, s);
+        encode(m, Dp, n, L, w, w.X, w.Y1, s);
+        hipLaunchKernelGGL(pool_kernel, dim3((unsigned)n), dim3(256), pool_lds, s, q, idf, d, Q, L, D, Dp, m->pad, (int64_t)n, w.X, w.QX, w.Y1, w.QY1,
+                           w.mcos, w.mctx, w.stats, extras ? extras + b0 * 4 : nullptr, bm25 ? bm25 + b0 : nullptr, m->q1_w, m->q1_b, m->wg_w, m->wg_b,
+                           out + b0, features_out ? features_out + b0 * Q * 6 : nullptr, stats_out ? stats_out + b0 * 3 : nullptr,
+                           qctx_out ? qctx_out + b0 * Q * 2 * D : nullptr, dctx_out ? dctx_out + b0 * (int64_t)L * 2 * D : nullptr);
+        return CAPAMD_OK;
+      });
 }
 
 }  // extern "C"

@@ -15,9 +15,8 @@
 // stay exactly 0 (LayerNorm normalises over the D real columns and writes 0 to the rest).
 #include "capreolus_amd.h"
 #include "tk_gemm.h"
-#include <hip/hip_runtime.h>
+#include "workspace.h"
 #include <math.h>
-#include <stdint.h>
 
 namespace {
 
@@ -365,7 +364,6 @@ __global__ __launch_bounds__(256) void pool_kernel(const int64_t* __restrict__ q
   }
 }
 
-int up64(int n) { return (n + 63) / 64 * 64; }
 int head_slot(int hd) { return (hd + 15) / 16 * 16; }
 
 struct Geo {
@@ -389,24 +387,17 @@ bool geometry(const capamd_tk_model* m, Geo* g) {
 
 bool shape_ok(const capamd_tk_model* m, int Q, int L) { return Q >= 1 && Q <= kMaxQ && L >= 1 && L <= m->max_len; }
 
-size_t up256(size_t n) { return (n + 255) / 256 * 256; }
-
 struct Ws {
   float *xq, *xd, *qkv, *ctx, *x1, *ff, *valid, *cos;
+  size_t bytes;
 };
 
 // workspace for nb documents: final rows of both sides, and one set of layer buffers for the longer side
-size_t ws_layout(const Geo& g, int64_t nb, int Q, int L, char* base, Ws* w) {
+Ws carve(const Geo& g, int64_t nb, int Q, int L, void* base) {
   const int64_t rows = nb * (int64_t)(L > Q ? L : Q);
-  const size_t sizes[8] = {(size_t)(nb * Q * g.Dp), (size_t)(nb * L * g.Dp), (size_t)(rows * 3 * g.Hs), (size_t)(rows * g.Hs),
-                           (size_t)(rows * g.Dp),   (size_t)(rows * g.Fp),    (size_t)rows,             (size_t)(nb * Q * L)};
-  float** ptrs[8] = {&w->xq, &w->xd, &w->qkv, &w->ctx, &w->x1, &w->ff, &w->valid, &w->cos};
-  size_t off = 0;
-  for (int i = 0; i < 8; ++i) {
-    if (base) *ptrs[i] = reinterpret_cast<float*>(base + off);
-    off += up256(sizes[i] * 4);
-  }
-  return off;
+  Carver c(base);
+  return {c.take(nb * Q * g.Dp), c.take(nb * L * g.Dp), c.take(rows * 3 * g.Hs), c.take(rows * g.Hs), c.take(rows * g.Dp),
+          c.take(rows * g.Fp),   c.take(rows),          c.take(nb * Q * L),      c.bytes()};
 }
 
 void launch_gemm_ln(const float* A, int64_t lda, int M, int N, int K, const float* W, const float* bias, const float* R, const float* gamma,
@@ -454,8 +445,6 @@ void encode(const capamd_tk_model* m, const Geo& g, const int64_t* ids, int64_t 
   }
 }
 
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -463,8 +452,7 @@ extern "C" {
 int64_t capamd_tk_workspace_bytes(const capamd_tk_model* m, int docs_per_microbatch, int Q, int L) {
   Geo g;
   if (!geometry(m, &g) || !shape_ok(m, Q, L) || docs_per_microbatch < 1) return -1;
-  Ws w;
-  return (int64_t)ws_layout(g, docs_per_microbatch, Q, L, nullptr, &w);
+  return (int64_t)carve(g, docs_per_microbatch, Q, L, nullptr).bytes;
 }
 
 int capamd_tk_forward(const int64_t* q_ids, const int64_t* d_ids, int B, int Q, int L, const capamd_tk_model* m, int docs_per_microbatch,
@@ -483,21 +471,17 @@ int capamd_tk_forward(const int64_t* q_ids, const int64_t* d_ids, int B, int Q, 
   if (B == 0) return CAPAMD_OK;
   const int64_t nb = docs_per_microbatch < B ? docs_per_microbatch : B;
   if (nb * (int64_t)(L > Q ? L : Q) > (int64_t)1 << 30) return CAPAMD_ERR_ARG;
-  Ws w;
-  if ((int64_t)ws_layout(g, nb, Q, L, nullptr, &w) > workspace_bytes) return CAPAMD_ERR_WORKSPACE;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return CAPAMD_ERR_ALIGN;
-  ws_layout(g, nb, Q, L, (char*)workspace, &w);
   hipStream_t s = (hipStream_t)stream;
-  (void)hipGetLastError();
-  for (int64_t b0 = 0; b0 < B; b0 += nb) {
-    const int64_t n = (B - b0) < nb ? (B - b0) : nb;
-    encode(m, g, q_ids + b0 * Q, n, Q, w, w.xq, status, CAPAMD_STATUS_QUERY_ID_RANGE, s);
-    encode(m, g, d_ids + b0 * L, n, L, w, w.xd, status, CAPAMD_STATUS_DOC_ID_RANGE, s);
-    hipLaunchKernelGGL(pool_kernel, dim3((unsigned)n), dim3(256), 0, s, q_ids + b0 * Q, d_ids + b0 * L, Q, L, w.xq, w.xd, g.Dp, m->emb, m->vocab, g.D,
-                       m->pad, m->mixer, m->alpha, m->s_log_w, m->s_len_w, m->comb_w, w.cos, out + b0,
-                       features_out ? features_out + b0 * 2 * kNumKernels : nullptr);
-  }
-  return hipGetLastError() == hipSuccess ? CAPAMD_OK : CAPAMD_ERR_LAUNCH;
+  return run_microbatches(
+      B, docs_per_microbatch, workspace, workspace_bytes, [&](int64_t n, void* base) { return carve(g, n, Q, L, base); },
+      [&](int64_t b0, int64_t n, const Ws& w) {
+        encode(m, g, q_ids + b0 * Q, n, Q, w, w.xq, status, CAPAMD_STATUS_QUERY_ID_RANGE, s);
+        encode(m, g, d_ids + b0 * L, n, L, w, w.xd, status, CAPAMD_STATUS_DOC_ID_RANGE, s);
+        hipLaunchKernelGGL(pool_kernel, dim3((unsigned)n), dim3(256), 0, s, q_ids + b0 * Q, d_ids + b0 * L, Q, L, w.xq, w.xd, g.Dp, m->emb, m->vocab,
+                           g.D, m->pad, m->mixer, m->alpha, m->s_log_w, m->s_len_w, m->comb_w, w.cos, out + b0,
+                           features_out ? features_out + b0 * 2 * kNumKernels : nullptr);
+        return CAPAMD_OK;
+      });
 }
 
 }  // extern "C"

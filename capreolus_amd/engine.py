@@ -1287,6 +1287,53 @@ class ParadeEngine:
         return (out, cls) if return_cls else out
 
 
+class _PerDocumentEngine:
+    """What the engines of the per-document rerankers share: the documents of a call run in micro-batches of `docs_per_microbatch`
+    (None: as many as the model's budget holds) on one workspace that only ever grows."""
+
+    def __init__(self, docs_per_microbatch=None):
+        self.docs_per_microbatch = docs_per_microbatch
+        self._ws = None
+
+    @staticmethod
+    def _ids(query, doc):
+        _need_gpu(query, doc)
+        q, d = _i64(query), _i64(doc)
+        B, Q = q.shape
+        if d.shape[0] != B:
+            raise ValueError(f"{B} query rows for {d.shape[0]} documents")
+        return q, d, B, Q, d.shape[1]
+
+    @staticmethod
+    def _fit(bytes_of, B, budget):
+        """the default micro-batch: as many documents as the budget holds, by what the second document adds to the first"""
+        return max(1, budget // max(1, bytes_of(2) - bytes_of(1)))
+
+    def _workspace(self, bytes_fn, m, device, B, Q, L, budget, refusal):
+        """-> (documents per micro-batch, the workspace that holds them) by the model's capamd_*_workspace_bytes; ValueError(refusal())
+        for a geometry the entry does not take"""
+        def bytes_of(nb):
+            return bytes_fn(ctypes.byref(m), nb, Q, L)
+
+        if bytes_of(1) < 0:
+            raise ValueError(refusal())
+        nb = self.docs_per_microbatch
+        if nb is None:
+            nb = self._fit(bytes_of, B, budget)
+        nb = max(1, min(int(nb), max(B, 1)))
+        need = bytes_of(nb)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
+        return nb, self._ws
+
+    @staticmethod
+    def _finish(rc, what, st, check):
+        _lib.check(rc, what)
+        if check:
+            st.raise_if_set()
+
+
 TK_WORKSPACE_BUDGET = 1 << 30      # bytes of activations per capamd_tk_forward call (documents run in micro-batches that fit)
 
 
@@ -1294,17 +1341,16 @@ def _up64(n):
     return (n + 63) // 64 * 64
 
 
-class TKEngine:
+class TKEngine(_PerDocumentEngine):
     """TK (reference TK.py, TK_class.forward) through capamd_tk_forward.  The encoder's weights are re-laid out once per set of weights
     into the padded layout of include/capreolus_amd.h (each head in its own 16-multiple slot, widths padded to 64 with zeros), kept
     until any parameter changes (storage pointers + version counters, as ConvProjectionTables); the embedding table and the `pe`
     buffer are read in place.  `docs_per_microbatch` (None: as many as TK_WORKSPACE_BUDGET holds) bounds the activations of a call."""
 
     def __init__(self, docs_per_microbatch=None):
-        self.docs_per_microbatch = docs_per_microbatch
+        super().__init__(docs_per_microbatch)
         self._key = None
         self._keep = None
-        self._ws = None
 
     @staticmethod
     def _layer_names(n):
@@ -1379,42 +1425,24 @@ class TKEngine:
 
     def forward(self, query, doc, params, heads, numlayers, usemask, alpha, pad, ln_eps=1e-5, mixer=None, features=False, check=True):
         """int64 query ids [B, Q], document ids [B, L] -> fp32 scores [B] (and the [B, 22] features s_log_k | s_len_k with features=True)"""
-        _need_gpu(query, doc)
-        q, d = _i64(query), _i64(doc)
-        B, Q = q.shape
-        L = d.shape[1]
-        if d.shape[0] != B:
-            raise ValueError(f"{B} query rows for {d.shape[0]} documents")
+        q, d, B, Q, L = self._ids(query, doc)
         m, keep = self.model(params, heads, numlayers, usemask, alpha, pad, ln_eps, mixer)
         lib = _lib.load()
-        one = lib.capamd_tk_workspace_bytes(ctypes.byref(m), 1, Q, L)
-        if one < 0:
-            raise ValueError(f"unsupported TK geometry: dim {m.dim}, heads {m.heads}, ffdim {m.ffdim}, layers {m.numlayers}, Q {Q}, L {L} "
-                             f"(dim <= 512, dim % heads == 0, dim / heads <= 64, ffdim <= 512, layers >= 1, Q <= 32, L <= {m.max_len})")
-        nb = self.docs_per_microbatch
-        if nb is None:
-            per_doc = max(1, lib.capamd_tk_workspace_bytes(ctypes.byref(m), 2, Q, L) - one)
-            nb = max(1, TK_WORKSPACE_BUDGET // per_doc)
-        nb = max(1, min(int(nb), max(B, 1)))
-        need = lib.capamd_tk_workspace_bytes(ctypes.byref(m), nb, Q, L)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != q.device:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        nb, ws = self._workspace(lib.capamd_tk_workspace_bytes, m, q.device, B, Q, L, TK_WORKSPACE_BUDGET, lambda: (
+                                 f"unsupported TK geometry: dim {m.dim}, heads {m.heads}, ffdim {m.ffdim}, layers {m.numlayers}, Q {Q}, L {L} "
+                                 f"(dim <= 512, dim % heads == 0, dim / heads <= 64, ffdim <= 512, layers >= 1, Q <= 32, L <= {m.max_len})"))
         out = torch.empty(B, dtype=torch.float32, device=q.device)
         feats = torch.empty((B, 22), dtype=torch.float32, device=q.device) if features else None
         st = status_word(q.device)
-        rc = lib.capamd_tk_forward(_ptr(q), _ptr(d), B, Q, L, ctypes.byref(m), nb, _ptr(self._ws), self._ws.numel(), _ptr(out), _ptr(feats),
-                                   _ptr(st.t), _stream())
-        _lib.check(rc, "capamd_tk_forward")
-        if check:
-            st.raise_if_set()
+        rc = lib.capamd_tk_forward(_ptr(q), _ptr(d), B, Q, L, ctypes.byref(m), nb, _ptr(ws), ws.numel(), _ptr(out), _ptr(feats), _ptr(st.t), _stream())
+        self._finish(rc, "capamd_tk_forward", st, check)
         return (out, feats) if features else out
 
 
 HINT_WORKSPACE_BUDGET = 1 << 30    # bytes of window-transposed inputs per capamd_hint_forward call (documents run in micro-batches that fit)
 
 
-class HintEngine:
+class HintEngine(_PerDocumentEngine):
     """HINT (reference HINT.py, HiNT_main.test_forward) through capamd_hint_forward.  Every parameter is read in place from the live
     tensors (nn.Linear / nn.LSTM layout): there is nothing to re-lay out and so nothing cached but the workspace.
     `docs_per_microbatch` (None: as many as HINT_WORKSPACE_BUDGET holds) bounds the workspace of a call."""
@@ -1425,10 +1453,6 @@ class HintEngine:
         (f"lstm_{k[0]}_{k[1]}{'_r' if rev else ''}", f"HiNT1.lstm.{'weight' if k[0] == 'w' else 'bias'}_{k[1]}_l0{rev}")
         for rev in ("", "_reverse") for k in (("w", "ih"), ("w", "hh"), ("b", "ih"), ("b", "hh"))) + (
         ("wv_w", "HiNT1.Wv.weight"), ("wv_b", "HiNT1.Wv.bias"), ("fc_w", "HiNT1.fc.weight"), ("fc_b", "HiNT1.fc.bias"))
-
-    def __init__(self, docs_per_microbatch=None):
-        self.docs_per_microbatch = docs_per_microbatch
-        self._ws = None
 
     def model(self, params, kmax):
         """the capamd_hint_model of these live parameters (the second item keeps what it points to alive)"""
@@ -1442,42 +1466,24 @@ class HintEngine:
 
     def forward(self, query, doc, params, kmax, evidence=False, check=True):
         """int64 query ids [B, Q], document ids [B, L] -> fp32 scores [B] (and the [B, L // 100, 8] window evidence with evidence=True)"""
-        _need_gpu(query, doc)
-        q, d = _i64(query), _i64(doc)
-        B, Q = q.shape
-        L = d.shape[1]
-        if d.shape[0] != B:
-            raise ValueError(f"{B} query rows for {d.shape[0]} documents")
+        q, d, B, Q, L = self._ids(query, doc)
         m, keep = self.model(params, kmax)
         lib = _lib.load()
-        one = lib.capamd_hint_workspace_bytes(ctypes.byref(m), 1, Q, L)
-        if one < 0:
-            raise ValueError(f"unsupported HINT geometry: dim {m.dim}, kmax {m.kmax}, Q {Q}, L {L} "
-                             f"(dim <= 512, Q <= 32, 100 <= L, L // 100 <= 64, 1 <= kmax <= min(2 (L // 100), 32))")
-        nb = self.docs_per_microbatch
-        if nb is None:
-            per_doc = max(1, lib.capamd_hint_workspace_bytes(ctypes.byref(m), 2, Q, L) - one)
-            nb = max(1, HINT_WORKSPACE_BUDGET // per_doc)
-        nb = max(1, min(int(nb), max(B, 1)))
-        need = lib.capamd_hint_workspace_bytes(ctypes.byref(m), nb, Q, L)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != q.device:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        nb, ws = self._workspace(lib.capamd_hint_workspace_bytes, m, q.device, B, Q, L, HINT_WORKSPACE_BUDGET, lambda: (
+                                 f"unsupported HINT geometry: dim {m.dim}, kmax {m.kmax}, Q {Q}, L {L} "
+                                 f"(dim <= 512, Q <= 32, 100 <= L, L // 100 <= 64, 1 <= kmax <= min(2 (L // 100), 32))"))
         out = torch.empty(B, dtype=torch.float32, device=q.device)
         ev = torch.empty((B, L // 100, 8), dtype=torch.float32, device=q.device) if evidence else None
         st = status_word(q.device)
-        rc = lib.capamd_hint_forward(_ptr(q), _ptr(d), B, Q, L, ctypes.byref(m), nb, _ptr(self._ws), self._ws.numel(), _ptr(out), _ptr(ev),
-                                     _ptr(st.t), _stream())
-        _lib.check(rc, "capamd_hint_forward")
-        if check:
-            st.raise_if_set()
+        rc = lib.capamd_hint_forward(_ptr(q), _ptr(d), B, Q, L, ctypes.byref(m), nb, _ptr(ws), ws.numel(), _ptr(out), _ptr(ev), _ptr(st.t), _stream())
+        self._finish(rc, "capamd_hint_forward", st, check)
         return (out, ev) if evidence else out
 
 
 POSIT_WORKSPACE_BUDGET = 6 << 30    # bytes of activations per capamd_posit_forward call: 1000 pairs of 4 x 800 terms at dim 300 fit at once
 
 
-class PositEngine:
+class PositEngine(_PerDocumentEngine):
     """POSITDRMM (reference POSITDRMM.py, POSITDRMM_class.test_forward) through capamd_posit_forward.  The LSTM's weights are packed
     into the kernels' padded, gate-interleaved layout once per parameter version (include/capreolus_amd.h); the embedding table, Q1 and
     Wg are read in place.  `docs_per_microbatch` (None: B in as few equal parts as POSIT_WORKSPACE_BUDGET allows) bounds the workspace."""
@@ -1486,10 +1492,18 @@ class PositEngine:
                   for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
 
     def __init__(self, docs_per_microbatch=None):
-        self.docs_per_microbatch = docs_per_microbatch
-        self._ws = None
+        super().__init__(docs_per_microbatch)
         self._key = None
         self._keep = None
+
+    @staticmethod
+    def _fit(bytes_of, B, budget):
+        """B in as few equal parts as the budget allows, beside the 512 MiB projection chunk; what a pair adds is read between large
+        micro-batches, where that chunk has reached its fixed size"""
+        per_doc = max(1, (bytes_of(1 << 16) - bytes_of(1 << 15)) >> 15)
+        most = max(1, (budget - (512 << 20)) // per_doc)
+        parts = -(-max(B, 1) // most)
+        return -(-max(B, 1) // parts)
 
     @staticmethod
     def _pack(params, D):
@@ -1550,21 +1564,8 @@ class PositEngine:
             raise ValueError(f"{B} query rows of {Q} terms for {d.shape[0]} documents, idf {tuple(idf.shape)}, {side.numel()} extra values")
         m, keep = self.model(params, pad)
         lib = _lib.load()
-        one = lib.capamd_posit_workspace_bytes(ctypes.byref(m), 1, Q, L)
-        if one < 0:
-            raise ValueError(f"unsupported POSITDRMM geometry: dim {m.dim}, Q {Q}, L {L} (dim <= 320, Q <= 16, 5 <= L <= 8192)")
-        nb = self.docs_per_microbatch
-        if nb is None:
-            # (between large micro-batches, where the projection chunk has reached its fixed size: what a pair adds)
-            per_doc = max(1, (lib.capamd_posit_workspace_bytes(ctypes.byref(m), 1 << 16, Q, L) - lib.capamd_posit_workspace_bytes(ctypes.byref(m), 1 << 15, Q, L)) >> 15)
-            most = max(1, (POSIT_WORKSPACE_BUDGET - (512 << 20)) // per_doc)
-            parts = -(-max(B, 1) // most)
-            nb = -(-max(B, 1) // parts)
-        nb = max(1, min(int(nb), max(B, 1)))
-        need = lib.capamd_posit_workspace_bytes(ctypes.byref(m), nb, Q, L)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != q.device:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        nb, ws = self._workspace(lib.capamd_posit_workspace_bytes, m, q.device, B, Q, L, POSIT_WORKSPACE_BUDGET, lambda: (
+            f"unsupported POSITDRMM geometry: dim {m.dim}, Q {Q}, L {L} (dim <= 320, Q <= 16, 5 <= L <= 8192)"))
         out = torch.empty(B, dtype=torch.float32, device=q.device)
         det = None
         if details:
@@ -1575,10 +1576,8 @@ class PositEngine:
                    "doc_context": torch.empty((B, L, 2 * D), dtype=torch.float32, device=q.device)}
         st = status_word(q.device)
         rc = lib.capamd_posit_forward(_ptr(q), _ptr(idf), _ptr(d), _ptr(side) if extras is not None else None, _ptr(side) if extras is None else None,
-                                      B, Q, L, ctypes.byref(m), nb, _ptr(self._ws), self._ws.numel(), _ptr(out),
+                                      B, Q, L, ctypes.byref(m), nb, _ptr(ws), ws.numel(), _ptr(out),
                                       *((_ptr(det[k]) for k in ("features", "stats", "query_context", "doc_context")) if details else (None,) * 4),
                                       _ptr(st.t), _stream())
-        _lib.check(rc, "capamd_posit_forward")
-        if check:
-            st.raise_if_set()
+        self._finish(rc, "capamd_posit_forward", st, check)
         return (out, det) if details else out
