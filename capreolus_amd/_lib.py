@@ -20,6 +20,7 @@ OK, ERR_ARG, ERR_ALIGN, ERR_LAUNCH, ERR_WORKSPACE = 0, 1, 2, 3, 4
 LAUNCH_CONCURRENT = 1
 STATUS_DOC_ID_RANGE, STATUS_QUERY_ID_RANGE, STATUS_QUERY_OOV, STATUS_SCORE_NAN, STATUS_TIE_RANGE, STATUS_LIST_QUERY = 1, 2, 4, 8, 16, 32
 STATUS_SHORT_DOC = 64
+STATUS_SEGMENT_RANGE = 128
 
 _vp, _i, _i64, _sz, _u, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_uint, ctypes.c_float
 
@@ -84,6 +85,16 @@ class PositModel(ctypes.Structure):
 
 _pop = ctypes.POINTER(PositModel)
 
+
+class DeepTileModel(ctypes.Structure):
+    """capamd_deeptile_model (include/capreolus_amd.h)."""
+
+    _fields_ = [("packed", ctypes.c_void_p), ("packed_floats", ctypes.c_int64)] + [
+        (n, ctypes.c_int) for n in ("maxqlen", "channels", "filters", "hidden", "lin1", "lin2")]
+
+
+_dtp = ctypes.POINTER(DeepTileModel)
+
 # name -> (restype, argtypes); must list every symbol include/capreolus_amd.h declares
 SIGNATURES = {
     "capamd_version": (_i, []),
@@ -143,6 +154,9 @@ SIGNATURES = {
     "capamd_hint_forward": (_i, [_vp, _vp, _i, _i, _i, _hnp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "capamd_posit_workspace_bytes": (_i64, [_pop, _i, _i, _i]),
     "capamd_posit_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _pop, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "capamd_deeptile_color": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "capamd_deeptile_packed_floats": (_i64, [_dtp]),
+    "capamd_deeptile_forward": (_i, [_vp, _i, _i, _i, _i, _dtp, _vp, _vp, _vp]),
     "capamd_maxp_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "capamd_bert_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "capamd_bert_gemm_ln": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

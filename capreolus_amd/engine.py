@@ -97,6 +97,9 @@ class StatusWord:
             if bits & (_lib.STATUS_SCORE_NAN | _lib.STATUS_TIE_RANGE):
                 raise ValueError("ranking: " + ("a score is NaN; " if bits & _lib.STATUS_SCORE_NAN else "") +
                                  ("a tie-break rank is outside 0..n-1" if bits & _lib.STATUS_TIE_RANGE else ""))
+            if bits & _lib.STATUS_SEGMENT_RANGE:
+                raise ValueError("DeepTileBar colouring: a segment offset decreases or leaves [0, L] (it was clamped; nothing was read outside "
+                                 "the row)")
             if bits & _lib.STATUS_SHORT_DOC:
                 raise ValueError("POSITDRMM: a document has fewer than 2 non-pad terms (the reference's match statistics divide by its "
                                  "length and by its number of bigrams)")
@@ -1581,3 +1584,81 @@ class PositEngine(_PerDocumentEngine):
                                       _ptr(st.t), _stream())
         self._finish(rc, "capamd_posit_forward", st, check)
         return (out, det) if details else out
+
+
+class DeepTileEngine(_PerDocumentEngine):
+    """DeepTileBar (reference DeepTileBar.py, DeepTileBar_class.test_forward; deeptileextractor.py, color_grid) through
+    capamd_deeptile_forward and capamd_deeptile_color.  The ten convolutions, ten LSTMs and three linear layers are laid out into the one
+    buffer of include/capreolus_amd.h once per set of weights, kept until any parameter changes (storage pointers + version counters, as
+    TKEngine); the embedding table of the colouring is read in place.  Neither call needs a workspace."""
+
+    WIDTHS = tuple(range(1, 11))
+
+    def __init__(self):
+        super().__init__()
+        self._key = None
+        self._keep = None
+
+    @classmethod
+    def names(cls):
+        """the state_dict names in the packed order"""
+        pre = "DeepTileBar1."
+        out = []
+        for w in cls.WIDTHS:
+            out += [f"{pre}conv{w}.weight", f"{pre}conv{w}.bias"] + [f"{pre}lstm{w}.{k}_l0" for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        return out + [f"{pre}W{n}.{k}" for n in (1, 2, 3) for k in ("weight", "bias")]
+
+    def model(self, params):
+        """the capamd_deeptile_model of these live parameters (packing again only when a parameter changed); the second item keeps what
+        it points to alive"""
+        names = self.names()
+        _need_gpu(*(params[k] for k in names))
+        key = tuple((params[k].data_ptr(), params[k]._version) for k in names)
+        if key != self._key:
+            self._keep = torch.cat([_f32(params[k].detach()).reshape(-1) for k in names])
+            self._key = key
+        conv, w_hh, w1, w2 = (params[f"DeepTileBar1.{k}"] for k in ("conv1.weight", "lstm1.weight_hh_l0", "W1.weight", "W2.weight"))
+        m = _lib.DeepTileModel()
+        m.packed, m.packed_floats = self._keep.data_ptr(), self._keep.numel()
+        m.filters, m.channels, m.maxqlen = conv.shape[0], conv.shape[1], conv.shape[2]
+        m.hidden, m.lin1, m.lin2 = w_hh.shape[1], w1.shape[0], w2.shape[0]
+        return m, self._keep
+
+    def forward(self, tiles, params, evidence=False):
+        """fp32 tiles [B, Q, P, C] -> fp32 scores [B] (and the [B, 10, hidden] last hidden states, the input of W1, with evidence=True)"""
+        _need_gpu(tiles)
+        if tiles.dim() != 4:
+            raise ValueError(f"tiles are [B, Q, P, C]; got {tuple(tiles.shape)}")
+        t = _f32(tiles)
+        B, Q, P, C = t.shape
+        m, keep = self.model(params)
+        lib = _lib.load()
+        if lib.capamd_deeptile_packed_floats(ctypes.byref(m)) != m.packed_floats or Q != m.maxqlen or C != m.channels or not 10 <= P <= 64:
+            raise ValueError(f"unsupported DeepTileBar geometry: tiles Q {Q}, P {P}, C {C} for a model of maxqlen {m.maxqlen}, {m.channels} channels, "
+                             f"{m.filters} filters, hidden {m.hidden}, linear {m.lin1} / {m.lin2} (Q and C as the model's, 10 <= P <= 64, "
+                             f"maxqlen <= 32, C in (2, 3), 3 filters, hidden <= 16, linear widths <= 128)")
+        out = torch.empty(B, dtype=torch.float32, device=t.device)
+        ev = torch.empty((B, 10, m.hidden), dtype=torch.float32, device=t.device) if evidence else None
+        rc = lib.capamd_deeptile_forward(_ptr(t), B, Q, P, C, ctypes.byref(m), _ptr(out), _ptr(ev), _stream())
+        _lib.check(rc, "capamd_deeptile_forward")
+        return (out, ev) if evidence else out
+
+    def color(self, query, doc, seg_start, idf, emb, channels=3, check=True):
+        """int64 query ids [B, Q], document ids [B, L], int32 segment offsets [B, P + 1], fp32 idf [B, Q], the fp32 table [V, D] -> fp32
+        tiles [B, Q, P, channels].  With check=True an id >= V raises IdRangeError and a clamped offset ValueError; with check=False the
+        tiles come back and the bits stay in the device's status word."""
+        _need_gpu(seg_start, idf, emb)
+        q, d, B, Q, L = self._ids(query, doc)
+        seg, w, e = _i32(seg_start), _f32(idf), _f32(emb)
+        P = seg.shape[1] - 1
+        if seg.shape[0] != B or tuple(w.shape) != (B, Q) or e.dim() != 2:
+            raise ValueError(f"{B} documents with segment offsets {tuple(seg.shape)}, idf {tuple(w.shape)}, table {tuple(e.shape)}")
+        if not (1 <= Q <= 32 and 1 <= P <= 64 and 1 <= e.shape[1] <= 512 and L >= 1 and channels in (2, 3)):
+            raise ValueError(f"unsupported colouring geometry: Q {Q}, P {P}, dim {e.shape[1]}, L {L}, channels {channels} "
+                             f"(Q <= 32, P <= 64, dim <= 512, channels in (2, 3))")
+        tiles = torch.empty((B, Q, P, channels), dtype=torch.float32, device=q.device)
+        st = status_word(q.device)
+        rc = _lib.load().capamd_deeptile_color(_ptr(q), _ptr(d), _ptr(seg), _ptr(w), B, Q, L, P, _ptr(e), e.shape[0], e.shape[1], channels, _ptr(tiles),
+                                               _ptr(st.t), _stream())
+        self._finish(rc, "capamd_deeptile_color", st, check)
+        return tiles

@@ -146,5 +146,6 @@ from .ptparade import PTParade, PTParade_Class  # noqa: E402,F401
 from .TK import TK, TK_class  # noqa: E402,F401
 from .HINT import HINT, HiNT_main  # noqa: E402,F401
 from .POSITDRMM import POSITDRMM, POSITDRMM_basic, POSITDRMM_class  # noqa: E402,F401
+from .DeepTileBar import DeepTileBar, DeepTileBar_class, DeepTileBar_nn  # noqa: E402,F401
 
 registry = {"KNRM": KNRM, "DRMM": DRMM, "DRMMTKS": DRMMTKS, "PACRR": PACRR, "ConvKNRM": ConvKNRM, "ptBERTMaxP": PTBERTMaxP, "CEDRKNRM": CEDRKNRM}

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CAPAMD_VERSION 405
+#define CAPAMD_VERSION 405   /* (the DeepTileBar entries below were added without a new number: purely additive, nothing existing changed) */
 
 #define CAPAMD_OK 0
 #define CAPAMD_ERR_ARG 1       /* null pointer / bad size / unsupported configuration */
@@ -46,6 +46,7 @@ extern "C" {
 #define CAPAMD_STATUS_LIST_QUERY 32    /* *_forward_lists: a pair of a list brings another query row (DRMM, DRMM-TKS: or another idf row) than
                                           the list's first pair - a list is ONE query against its documents */
 #define CAPAMD_STATUS_SHORT_DOC 64     /* capamd_posit_forward: a document of fewer than 2 non-pad terms (the reference divides by zero) */
+#define CAPAMD_STATUS_SEGMENT_RANGE 128 /* capamd_deeptile_color: a segment offset decreases or leaves [0, L] (clamped; nothing is read outside the row) */
 
 /* library identity */
 int capamd_version(void);
@@ -520,6 +521,48 @@ int64_t capamd_posit_workspace_bytes(const capamd_posit_model* m, int docs_per_m
 int capamd_posit_forward(const int64_t* q_ids, const float* q_idf, const int64_t* d_ids, const float* extras, const float* bm25, int B, int Q, int L,
                          const capamd_posit_model* m, int docs_per_microbatch, void* workspace, int64_t workspace_bytes, float* out,
                          float* features_out, float* stats_out, float* qctx_out, float* dctx_out, int* status, void* stream);
+
+/* ---- DeepTileBar (reference capreolus/extractor/deeptileextractor.py, create_visualization_matrix -> color_grid, and
+ * capreolus/reranker/DeepTileBar.py, DeepTileBar_class.test_forward) -----------------------------------------------------------------
+ * Text tiling itself (nltk.TextTilingTokenizer) stays with the caller: these entries take its segment boundaries.
+ *
+ * capamd_deeptile_color: term ids + segment boundaries -> tiles_out [B][Q][P][C] fp32, the reference's color_grid, quirks included.
+ *   q_ids int64 [B][Q] (pad = 0), d_ids int64 [B][L], seg_start int32 [B][P + 1] (segment p of document b is
+ *   d_ids[b][seg_start[b][p] .. seg_start[b][p + 1]); the offsets need not cover the row: tokens outside [start[0], start[P]) are
+ *   ignored), idf fp32 [B][Q], emb fp32 [V][D] read in place, C = 3 or 2 (the extractor's `tfchannel` false).  Per (query term q, segment):
+ *     q == 0 (a pad query term) or an empty segment (start[p] == start[p + 1]: how the host encodes the literal "<pad>" segment that
+ *     padlist appends): zeros;  otherwise tf = the segment's tokens whose id equals q, channels [tf, idf if tf else 0, sim] (C = 3) or
+ *     [idf if tf else 0, sim] (C = 2), sim = max over the segment's tokens of exp(-|emb[t] - emb[q]|^2 / 2), the squared distance summed
+ *     from the differences (not |x|^2 + |z|^2 - 2 x.z), accurate expf;
+ *     a token with a NEGATIVE id (the literal "<pad>" token) contributes exactly 0 and is never counted in tf; a token with id 0 (every
+ *     word stoi does not know: stoi.get(tok, pad)) is looked up like any other and contributes exp(-|emb[q]|^2 / 2), not 0.
+ *   Ids >= V count as the zero row and set CAPAMD_STATUS_DOC_ID_RANGE / _QUERY_ID_RANGE (a negative query id likewise).  Offsets that
+ *   decrease or leave [0, L] are clamped to min(L, max(0, start[0..p])) and set CAPAMD_STATUS_SEGMENT_RANGE.
+ *   Limits: 1 <= Q <= 32, 1 <= P <= 64, 1 <= D <= 512, L >= 1 (CAPAMD_ERR_ARG beyond them).  No workspace.
+ *
+ * capamd_deeptile_forward: tiles [B][Q][P][C] -> out [B], one launch; evidence_out (optional) [B][10][hidden]: the last hidden state of
+ * each LSTM in order 1 .. 10, the input of W1.  Per document, the tile seen as [C][Q][P]: conv_w (w = 1 .. 10; kernel (Q, w), 3
+ * filters, bias, no activation) gives a sequence of T_w = P - w + 1 steps of 3 values; lstm_w (gates i, f, g, o, both biases, zero
+ * state) runs over it and only its last h is kept; the ten h concatenated; relu(W1 .), relu(W2 .), W3.
+ * The parameters come as ONE fp32 buffer `packed` of capamd_deeptile_packed_floats(m) floats (-1: a configuration that is refused),
+ * laid out by the caller once per parameter version: per width w = 1 .. 10 [conv_w.weight [3][C][Q][w] | conv_w.bias [3] |
+ * lstm_w.weight_ih_l0 [4 hidden][3] | weight_hh_l0 [4 hidden][hidden] | bias_ih_l0 [4 hidden] | bias_hh_l0 [4 hidden]], then
+ * W1.weight [lin1][10 hidden] | W1.bias | W2.weight [lin2][lin1] | W2.bias | W3.weight [lin2] | W3.bias [1].
+ * Limits (CAPAMD_ERR_ARG, nothing is launched): filters == 3 (the reference hard-codes nn.LSTM(input_size=3)), 10 <= P <= 64 (conv10
+ * needs ten columns), Q == maxqlen, 1 <= maxqlen <= 32, C == channels in {2, 3}, 1 <= hidden <= 16, 1 <= lin1, lin2 <= 128,
+ * packed_floats == capamd_deeptile_packed_floats(m).  No workspace: a document's tile is about 1 KB.  Each document's score is
+ * independent of the other documents of the call, bit for bit. */
+typedef struct capamd_deeptile_model {
+  const float* packed;                   /* the layout above */
+  int64_t packed_floats;
+  int maxqlen, channels, filters, hidden, lin1, lin2;
+} capamd_deeptile_model;
+
+int capamd_deeptile_color(const int64_t* q_ids, const int64_t* d_ids, const int* seg_start, const float* idf, int B, int Q, int L, int P,
+                          const float* emb, int64_t V, int D, int C, float* tiles_out, int* status, void* stream);
+int64_t capamd_deeptile_packed_floats(const capamd_deeptile_model* m);
+int capamd_deeptile_forward(const float* tiles, int B, int Q, int P, int C, const capamd_deeptile_model* m, float* out, float* evidence_out,
+                            void* stream);
 
 /* ---- ConvKNRM ------------------------------------------------------------------------
  * Replaces ConvKNRM_class.forward, capreolus/reranker/ConvKNRM.py:42-77 (called from ConvKNRM.test :112-116).
