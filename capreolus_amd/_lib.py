@@ -21,6 +21,7 @@ LAUNCH_CONCURRENT = 1
 STATUS_DOC_ID_RANGE, STATUS_QUERY_ID_RANGE, STATUS_QUERY_OOV, STATUS_SCORE_NAN, STATUS_TIE_RANGE, STATUS_LIST_QUERY = 1, 2, 4, 8, 16, 32
 STATUS_SHORT_DOC = 64
 STATUS_SEGMENT_RANGE = 128
+STATUS_BAG_RANGE = 256
 
 _vp, _i, _i64, _sz, _u, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_uint, ctypes.c_float
 
@@ -95,6 +96,16 @@ class DeepTileModel(ctypes.Structure):
 
 _dtp = ctypes.POINTER(DeepTileModel)
 
+
+class DssmModel(ctypes.Structure):
+    """capamd_dssm_model (include/capreolus_amd.h)."""
+
+    _fields_ = [("w1t", ctypes.c_void_p), ("b1", ctypes.c_void_p), ("w", ctypes.c_void_p * 3), ("b", ctypes.c_void_p * 3), ("nvocab", ctypes.c_int64),
+                ("layers", ctypes.c_int), ("width", ctypes.c_int * 4)]
+
+
+_dsp = ctypes.POINTER(DssmModel)
+
 # name -> (restype, argtypes); must list every symbol include/capreolus_amd.h declares
 SIGNATURES = {
     "capamd_version": (_i, []),
@@ -157,6 +168,9 @@ SIGNATURES = {
     "capamd_deeptile_color": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "capamd_deeptile_packed_floats": (_i64, [_dtp]),
     "capamd_deeptile_forward": (_i, [_vp, _i, _i, _i, _i, _dtp, _vp, _vp, _vp]),
+    "capamd_cdssm_tower": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "capamd_dssm_tower": (_i, [_vp, _vp, _vp, _i64, _i64, _dsp, _i, _vp, _vp, _vp]),
+    "capamd_cos_sigmoid_pairs": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
     "capamd_maxp_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "capamd_bert_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "capamd_bert_gemm_ln": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

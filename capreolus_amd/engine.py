@@ -100,6 +100,9 @@ class StatusWord:
             if bits & _lib.STATUS_SEGMENT_RANGE:
                 raise ValueError("DeepTileBar colouring: a segment offset decreases or leaves [0, L] (it was clamped; nothing was read outside "
                                  "the row)")
+            if bits & _lib.STATUS_BAG_RANGE:
+                raise ValueError("DSSM: an indptr pair of the bags decreases or leaves [0, nnz] (it was clamped; nothing was read outside "
+                                 "idx / val)")
             if bits & _lib.STATUS_SHORT_DOC:
                 raise ValueError("POSITDRMM: a document has fewer than 2 non-pad terms (the reference's match statistics divide by its "
                                  "length and by its number of bigrams)")
@@ -1662,3 +1665,117 @@ class DeepTileEngine(_PerDocumentEngine):
                                                _ptr(st.t), _stream())
         self._finish(rc, "capamd_deeptile_color", st, check)
         return tiles
+
+
+QUERY_SIDE, DOC_SIDE = 0, 1        # the `side` of the tower entries: which id-range bit a bad id sets
+
+
+def cos_sigmoid_pairs(qrep, drep, pair_q=None, pair_d=None, check=True):
+    """fp32 tower outputs qrep [Nq, R], drep [Nd, R] (and int32 row indices [n_pairs]; None: pair i is row i) -> fp32 scores
+    sigmoid(cos) [n_pairs] through capamd_cos_sigmoid_pairs"""
+    _need_gpu(qrep, drep, pair_q, pair_d)
+    q, d = _f32(qrep), _f32(drep)
+    if q.dim() != 2 or d.dim() != 2 or q.shape[1] != d.shape[1]:
+        raise ValueError(f"tower outputs of shapes {tuple(q.shape)} and {tuple(d.shape)}")
+    pq, pd = (None if p is None else _i32(p).reshape(-1) for p in (pair_q, pair_d))
+    n = pq.numel() if pq is not None else pd.numel() if pd is not None else q.shape[0]
+    if (pq is not None and pd is not None and pq.numel() != pd.numel()) or (pq is None and n > q.shape[0]) or (pd is None and n > d.shape[0]):
+        raise ValueError(f"{n} pairs for {q.shape[0]} query rows and {d.shape[0]} document rows: without an index array pair i is row i")
+    out = torch.empty(n, dtype=torch.float32, device=q.device)
+    st = status_word(q.device)
+    rc = _lib.load().capamd_cos_sigmoid_pairs(_ptr(q), _ptr(d), _ptr(pq), _ptr(pd), q.shape[0], d.shape[0], n, q.shape[1], _ptr(out), _ptr(st.t), _stream())
+    _PerDocumentEngine._finish(rc, "capamd_cos_sigmoid_pairs", st, check)
+    return out
+
+
+class CdssmEngine:
+    """CDSSM (reference CDSSM.py, CDSSM_class.forward) through capamd_cdssm_tower, once per side, and capamd_cos_sigmoid_pairs.  The
+    embedding table and the convolution are read in place from the live tensors: there is nothing to re-lay out, and no workspace
+    beyond the two tower outputs."""
+
+    @staticmethod
+    def tower(ids, params, windowsize, side, check=True):
+        """int64 ids [N, T] -> fp32 [N, windowsize dim - nkernel + 1], the max over windows and filters, not normalised"""
+        _need_gpu(ids)
+        x = _i64(ids)
+        if x.dim() != 2:
+            raise ValueError(f"term ids are [N, T]; got {tuple(x.shape)}")
+        emb, w, b = (_f32(params[k].detach()) for k in ("embedding.weight", "conv.0.weight", "conv.0.bias"))
+        _need_gpu(emb, w, b)
+        N, T = x.shape
+        V, D = emb.shape
+        F, nk, W = w.shape[0], w.shape[2], int(windowsize)
+        if not (1 <= D <= 512 and 1 <= W <= 8 and W * D <= 4096 and 1 <= nk <= min(16, W * D) and 1 <= F <= 16 and T >= 1):
+            raise ValueError(f"unsupported CDSSM geometry: dim {D}, windowsize {W}, nkernel {nk}, nfilter {F}, T {T} (dim <= 512, windowsize <= 8, "
+                             f"windowsize dim <= 4096, nkernel <= min(16, windowsize dim), nfilter <= 16, T >= 1)")
+        rep = torch.empty((N, W * D - nk + 1), dtype=torch.float32, device=x.device)
+        st = status_word(x.device)
+        rc = _lib.load().capamd_cdssm_tower(_ptr(x), N, T, _ptr(emb), V, D, W, _ptr(w), _ptr(b), nk, F, side, _ptr(rep), _ptr(st.t), _stream())
+        _PerDocumentEngine._finish(rc, "capamd_cdssm_tower", st, check)
+        return rep
+
+    def forward(self, query, doc, params, windowsize, pair_q=None, pair_d=None, towers=False, check=True):
+        """int64 query ids [Nq, Q], document ids [Nd, L] -> fp32 scores (pair i = row i of both, or the int32 index arrays' pairs); with
+        towers=True also the two tower outputs"""
+        if pair_q is None and pair_d is None and query.shape[0] != doc.shape[0]:
+            raise ValueError(f"{query.shape[0]} query rows for {doc.shape[0]} documents")
+        qrep = self.tower(query, params, windowsize, QUERY_SIDE, check)
+        drep = self.tower(doc, params, windowsize, DOC_SIDE, check)
+        out = cos_sigmoid_pairs(qrep, drep, pair_q, pair_d, check)
+        return (out, qrep, drep) if towers else out
+
+
+class DssmEngine:
+    """DSSM (reference DSSM.py, DSSM_class.forward) through capamd_dssm_tower, once per side, and capamd_cos_sigmoid_pairs.  The first
+    layer is transposed and its rows padded to a multiple of 64 floats once per set of weights, kept until that parameter changes
+    (storage pointer + version counter, as TKEngine); the other layers are read in place.  No workspace beyond the two tower outputs."""
+
+    def __init__(self):
+        self._key = None
+        self._w1t = None
+
+    def model(self, linears):
+        """the capamd_dssm_model of the live (weight, bias) pairs of ffw.linear0 ..; the second item keeps what it points to alive"""
+        if not 1 <= len(linears) <= 4:
+            raise ValueError(f"DSSM takes 1 to 4 layers; got {len(linears)}")
+        keep = [(_f32(w.detach()), _f32(b.detach())) for w, b in linears]
+        _need_gpu(*(t for wb in keep for t in wb))
+        w1 = linears[0][0]
+        key = (w1.data_ptr(), w1._version, tuple(w1.shape))
+        if key != self._key:
+            h1, nvocab = w1.shape
+            w1t = torch.zeros((nvocab, _up64(h1)), dtype=torch.float32, device=w1.device)
+            w1t[:, :h1] = keep[0][0].t()
+            self._w1t, self._key = w1t, key
+        m = _lib.DssmModel()
+        m.w1t, m.b1 = self._w1t.data_ptr(), keep[0][1].data_ptr()
+        m.nvocab, m.layers = self._w1t.shape[0], len(keep)
+        for l, (w, b) in enumerate(keep):
+            m.width[l] = w.shape[0]
+            if l:
+                m.w[l - 1], m.b[l - 1] = w.data_ptr(), b.data_ptr()
+        return m, (keep, self._w1t)
+
+    def tower(self, bags, linears, side, check=True):
+        """Bags of N rows -> fp32 [N, last width], the output of the last ReLU, not normalised"""
+        indptr, idx, val = _i64(bags.indptr), _i32(bags.idx), _f32(bags.val)
+        _need_gpu(indptr, idx, val)
+        m, keep = self.model(linears)
+        N = indptr.numel() - 1
+        if N < 0 or idx.numel() != val.numel():
+            raise ValueError(f"bags with indptr of {indptr.numel()} entries, {idx.numel()} indices and {val.numel()} values")
+        rep = torch.empty((N, m.width[m.layers - 1]), dtype=torch.float32, device=indptr.device)
+        st = status_word(indptr.device)
+        rc = _lib.load().capamd_dssm_tower(_ptr(indptr), _ptr(idx), _ptr(val), N, idx.numel(), ctypes.byref(m), side, _ptr(rep), _ptr(st.t), _stream())
+        _PerDocumentEngine._finish(rc, "capamd_dssm_tower", st, check)
+        return rep
+
+    def forward(self, query, doc, linears, pair_q=None, pair_d=None, towers=False, check=True):
+        """query Bags, document Bags -> fp32 scores (pair i = row i of both, or the int32 index arrays' pairs); with towers=True also
+        the two tower outputs"""
+        if pair_q is None and pair_d is None and query.rows != doc.rows:
+            raise ValueError(f"{query.rows} query bags for {doc.rows} document bags")
+        qrep = self.tower(query, linears, QUERY_SIDE, check)
+        drep = self.tower(doc, linears, DOC_SIDE, check)
+        out = cos_sigmoid_pairs(qrep, drep, pair_q, pair_d, check)
+        return (out, qrep, drep) if towers else out

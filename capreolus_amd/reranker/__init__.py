@@ -147,5 +147,7 @@ from .TK import TK, TK_class  # noqa: E402,F401
 from .HINT import HINT, HiNT_main  # noqa: E402,F401
 from .POSITDRMM import POSITDRMM, POSITDRMM_basic, POSITDRMM_class  # noqa: E402,F401
 from .DeepTileBar import DeepTileBar, DeepTileBar_class, DeepTileBar_nn  # noqa: E402,F401
+from .DSSM import DSSM, DSSM_class  # noqa: E402,F401
+from .CDSSM import CDSSM, CDSSM_class  # noqa: E402,F401
 
 registry = {"KNRM": KNRM, "DRMM": DRMM, "DRMMTKS": DRMMTKS, "PACRR": PACRR, "ConvKNRM": ConvKNRM, "ptBERTMaxP": PTBERTMaxP, "CEDRKNRM": CEDRKNRM}

@@ -47,6 +47,7 @@ extern "C" {
                                           the list's first pair - a list is ONE query against its documents */
 #define CAPAMD_STATUS_SHORT_DOC 64     /* capamd_posit_forward: a document of fewer than 2 non-pad terms (the reference divides by zero) */
 #define CAPAMD_STATUS_SEGMENT_RANGE 128 /* capamd_deeptile_color: a segment offset decreases or leaves [0, L] (clamped; nothing is read outside the row) */
+#define CAPAMD_STATUS_BAG_RANGE 256     /* capamd_dssm_tower: an indptr pair decreases or leaves [0, nnz] (clamped; nothing is read outside idx / val) */
 
 /* library identity */
 int capamd_version(void);
@@ -563,6 +564,55 @@ int capamd_deeptile_color(const int64_t* q_ids, const int64_t* d_ids, const int*
 int64_t capamd_deeptile_packed_floats(const capamd_deeptile_model* m);
 int capamd_deeptile_forward(const float* tiles, int B, int Q, int P, int C, const capamd_deeptile_model* m, float* out, float* evidence_out,
                             void* stream);
+
+/* ---- DSSM and CDSSM (reference capreolus/reranker/DSSM.py, DSSM_class.forward, and CDSSM.py, CDSSM_class.forward) -------------------
+ * Both models are score = sigmoid(cos(tower(query), tower(document))): a tower runs once per distinct row, pairs are scored from the
+ * tower outputs.  `side` (0: query rows, 1: document rows) only chooses the status bit of an id outside its table (_QUERY_ID_RANGE /
+ * _DOC_ID_RANGE).  fp32 throughout, no workspace.  A row's tower output does not depend on N or on the other rows of the call, bit
+ * for bit.
+ *
+ * capamd_cdssm_tower: ids int64 [N][T] -> rep [N][R] fp32, R = windowsize dim - nkernel + 1, not normalised.  x = emb[ids] (row 0 is read
+ *   as the table has it: nothing masks pads), windowsize - T % windowsize zero rows appended (never none: a T that is a multiple gets a
+ *   whole window of zeros), the rows cut into K = T / windowsize + 1 windows of windowsize dim floats each, and
+ *     rep[t] = max over windows i and filters f of relu(b_f + sum_j w[f][j] x_i[t + j]),  j = 0 .. nkernel - 1,
+ *   the taps running across word boundaries inside a window, summed as one fmaf chain from the bias in the order of j.
+ *   emb [vocab][dim] is read in place (16-byte aligned), conv_w [nfilter][nkernel] (Conv1d(1, nfilter, nkernel).weight), conv_b [nfilter].
+ *   An id outside [0, vocab) counts as a zero row and sets the side's bit.
+ *   Limits (CAPAMD_ERR_ARG, nothing is launched): 1 <= dim <= 512, 1 <= windowsize <= 8, windowsize dim <= 4096,
+ *   1 <= nkernel <= min(16, windowsize dim), 1 <= nfilter <= 16, T >= 1, 0 <= N < 2^31, side 0 or 1.
+ *
+ * capamd_dssm_tower: bags of words in CSR form - indptr int64 [N + 1], idx int32 [nnz], val fp32 [nnz]; bag n is the entries
+ *   indptr[n] .. indptr[n + 1] - 1 - -> rep [N][width[layers - 1]] fp32, the output of the last ReLU, not normalised:
+ *     h_1 = relu(b1 + sum_k val_k W1^T[idx_k]),  h_l = relu(W_l h_(l-1) + b_l).
+ *   w1t [nvocab][h1p] is ffw.linear0.weight transposed, its rows padded with zeros to h1p = width[0] rounded up to 64 floats (16-byte
+ *   aligned; built once per set of weights by the caller); b1 [width[0]]; w[l - 1] [width[l]][width[l - 1]] and b[l - 1] [width[l]] are
+ *   ffw.linear<l> as nn.Linear has them, l = 1 .. layers - 1.  The first layer's sum runs in an order that is a function of the bag alone
+ *   (entry k on wave k % 4 in the order of k; the four partial sums added in wave order onto the bias): no float atomics.  An empty
+ *   bag is legal (h_1 = relu(b1)).  An idx outside [0, nvocab) is skipped and sets the side's bit; an indptr pair that decreases or
+ *   leaves [0, nnz] is clamped (lo into [0, nnz], hi into [lo, nnz]) and sets CAPAMD_STATUS_BAG_RANGE.
+ *   Limits (CAPAMD_ERR_ARG): 1 <= layers <= 4, 1 <= width[l] <= 512, 1 <= nvocab < 2^31, 0 <= N < 2^31, side 0 or 1.
+ *
+ * capamd_cos_sigmoid_pairs: out[i] = sigmoid(dot(q / (|q| + 1e-7), d / (|d| + 1e-7))) of q = qrep[pair_q[i]] ([Nq][R]) and
+ *   d = drep[pair_d[i]] ([Nd][R]), each side normalised on its own; pair_q / pair_d int32 [n_pairs], or NULL: then row i (n_pairs <= the
+ *   table's rows).  A pair's bits depend on its two rows alone: one query against N documents through the index arrays gives what the
+ *   query row repeated N times gives.  An index outside its table counts as a zero row and sets _QUERY_ID_RANGE / _DOC_ID_RANGE.  Two
+ *   all-zero rows score exactly 0.5. */
+typedef struct capamd_dssm_model {
+  const float* w1t;                      /* [nvocab][h1p]   ffw.linear0.weight, transposed and padded (above) */
+  const float* b1;                       /* [width[0]]      ffw.linear0.bias */
+  const float* w[3];                     /* ffw.linear1 .. linear3 .weight, as nn.Linear has them */
+  const float* b[3];
+  int64_t nvocab;
+  int layers;
+  int width[4];
+} capamd_dssm_model;
+
+int capamd_cdssm_tower(const int64_t* ids, int64_t N, int T, const float* emb, int64_t vocab, int dim, int windowsize, const float* conv_w,
+                       const float* conv_b, int nkernel, int nfilter, int side, float* rep, int* status, void* stream);
+int capamd_dssm_tower(const int64_t* indptr, const int* idx, const float* val, int64_t N, int64_t nnz, const capamd_dssm_model* m, int side, float* rep,
+                      int* status, void* stream);
+int capamd_cos_sigmoid_pairs(const float* qrep, const float* drep, const int* pair_q, const int* pair_d, int64_t Nq, int64_t Nd, int64_t n_pairs, int R,
+                             float* out, int* status, void* stream);
 
 /* ---- ConvKNRM ------------------------------------------------------------------------
  * Replaces ConvKNRM_class.forward, capreolus/reranker/ConvKNRM.py:42-77 (called from ConvKNRM.test :112-116).
