@@ -106,6 +106,17 @@ class DssmModel(ctypes.Structure):
 
 _dsp = ctypes.POINTER(DssmModel)
 
+
+class DuetModel(ctypes.Structure):
+    """capamd_duet_model (include/capreolus_amd.h)."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("emb", "lm_wt", "lm_b", "lm_w0", "lm_b0", "lm_w3", "lm_b3", "q_w", "q_b", "qf_w", "qf_b", "d_w1t", "d_b1",
+                                               "d_w2", "d_b2", "f1_w", "f1_b", "f2_w", "f2_b")] + [("vocab", ctypes.c_int64)] + [
+        (n, ctypes.c_int) for n in ("dim", "nfilters", "lmhidden", "maxdoclen", "nhidden", "activation", "idfweight")]
+
+
+_dup = ctypes.POINTER(DuetModel)
+
 # name -> (restype, argtypes); must list every symbol include/capreolus_amd.h declares
 SIGNATURES = {
     "capamd_version": (_i, []),
@@ -171,6 +182,8 @@ SIGNATURES = {
     "capamd_cdssm_tower": (_i, [_vp, _i64, _i, _vp, _i64, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "capamd_dssm_tower": (_i, [_vp, _vp, _vp, _i64, _i64, _dsp, _i, _vp, _vp, _vp]),
     "capamd_cos_sigmoid_pairs": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
+    "capamd_duet_workspace_bytes": (_i64, [_dup, _i, _i, _i]),
+    "capamd_duet_forward": (_i, [_vp, _vp, _vp, _i, _i, _i, _dup, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "capamd_maxp_pool": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "capamd_bert_gemm": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "capamd_bert_gemm_ln": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),

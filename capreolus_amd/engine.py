@@ -1667,6 +1667,83 @@ class DeepTileEngine(_PerDocumentEngine):
         return tiles
 
 
+DUET_WORKSPACE_BUDGET = 1 << 30    # bytes of per-token projections per capamd_duet_forward call (documents run in micro-batches that fit)
+
+
+class DuetEngine(_PerDocumentEngine):
+    """DUET (reference DUET.py, DUET_class.forward) through capamd_duet_forward.  Two weights are re-laid out once per parameter version
+    (storage pointers + version counters, as DeepTileEngine): the local model's convolution transposed to [maxdoclen, H], and d_conv1 as
+    per-token projections [dim up to 32, 3 H up to 16] (include/capreolus_amd.h); everything else is read in place.
+    `activation` ("relu" / "tanh") and `idfweight` are the plugin's config; `docs_per_microbatch` (None: as many as DUET_WORKSPACE_BUDGET
+    holds) bounds the workspace of a call."""
+
+    _FIELDS = (("emb", "dm.embedding.weight"), ("lm_b", "lm.conv.0.bias"), ("lm_w0", "lm.ffw.0.weight"), ("lm_b0", "lm.ffw.0.bias"),
+               ("lm_w3", "lm.ffw.3.weight"), ("lm_b3", "lm.ffw.3.bias"), ("q_w", "dm.q_conv.0.weight"), ("q_b", "dm.q_conv.0.bias"),
+               ("qf_w", "dm.q_ffw.0.weight"), ("qf_b", "dm.q_ffw.0.bias"), ("d_b1", "dm.d_conv1.0.bias"), ("d_w2", "dm.d_conv2.0.weight"),
+               ("d_b2", "dm.d_conv2.0.bias"), ("f1_w", "dm.ffw_1.0.weight"), ("f1_b", "dm.ffw_1.0.bias"), ("f2_w", "dm.ffw_2.1.weight"),
+               ("f2_b", "dm.ffw_2.1.bias"))
+    _PACKED = ("lm.conv.0.weight", "dm.d_conv1.0.weight")
+
+    def __init__(self, activation="relu", idfweight=True, docs_per_microbatch=None):
+        super().__init__(docs_per_microbatch)
+        self.activation = {"relu": 0, "tanh": 1}[activation]
+        self.idfweight = int(bool(idfweight))
+        self._key = None
+        self._packed = None
+
+    @staticmethod
+    def _pack(lm_w, d_w1):
+        """(lm.conv.0.weight [H, 1, 1, L] -> [L, H]; dm.d_conv1.0.weight [H, 1, 3, dim] -> [dim up to 32, 3 H up to 16], column j H + h)"""
+        H, _, _, D = d_w1.shape
+        w1t = torch.zeros((D + 31) // 32 * 32, (3 * H + 15) // 16 * 16, dtype=torch.float32, device=d_w1.device)
+        w1t[:D, :3 * H] = _f32(d_w1.detach()).view(H, 3, D).permute(2, 1, 0).reshape(D, 3 * H)
+        return _f32(lm_w.detach()).view(lm_w.shape[0], -1).t().contiguous(), w1t
+
+    def model(self, params):
+        """the capamd_duet_model of these live parameters (re-laying out the two packed weights only when one of them changed); the second
+        item keeps what it points to alive"""
+        keep = {f: _f32(params[name].detach()) for f, name in self._FIELDS}
+        _need_gpu(*keep.values(), *(params[k] for k in self._PACKED))
+        key = tuple((params[k].data_ptr(), params[k]._version) for k in self._PACKED)
+        if key != self._key:
+            self._packed = self._pack(*(params[k] for k in self._PACKED))
+            self._key = key
+        m = _lib.DuetModel()
+        for f, t in keep.items():
+            setattr(m, f, t.data_ptr())
+        m.lm_wt, m.d_w1t = (t.data_ptr() for t in self._packed)
+        m.vocab, m.dim = keep["emb"].shape
+        m.nfilters, m.lmhidden = keep["d_b1"].shape[0], keep["lm_b0"].shape[0]
+        m.maxdoclen, m.nhidden = self._packed[0].shape[0], keep["f1_w"].shape[1]
+        m.activation, m.idfweight = self.activation, self.idfweight
+        return m, (keep, self._packed)
+
+    def forward(self, query, query_idf, doc, params, parts=False, evidence=False, check=True):
+        """int64 query ids [B, 4], fp32 idf [B, 4], document ids [B, L] -> fp32 scores [B]; with parts=True also (lm, dm) [B, 2]; with
+        evidence=True also the query vector [B, H] and the pooled map [B, H, L - 101] (views of one buffer)"""
+        _need_gpu(query_idf)
+        q, d, B, Q, L = self._ids(query, doc)
+        idf = _f32(query_idf)
+        if tuple(idf.shape) != (B, Q):
+            raise ValueError(f"{B} query rows of {Q} terms with idf {tuple(idf.shape)}")
+        m, keep = self.model(params)
+        lib = _lib.load()
+        nb, ws = self._workspace(lib.capamd_duet_workspace_bytes, m, q.device, B, Q, L, DUET_WORKSPACE_BUDGET, lambda: (
+            f"unsupported DUET geometry: Q {Q}, L {L}, nfilters {m.nfilters}, lmhidden {m.lmhidden}, dim {m.dim}, maxdoclen {m.maxdoclen}, "
+            f"nhidden {m.nhidden} (Q == 4, 2 <= nfilters <= 32, 1 <= lmhidden <= 256, dim <= 512, 103 <= L <= 8192, L == maxdoclen, "
+            f"nhidden == L - 101)"))
+        H, NP = m.nfilters, L - 101
+        out = torch.empty(B, dtype=torch.float32, device=q.device)
+        pt = torch.empty((B, 2), dtype=torch.float32, device=q.device) if parts else None
+        ev = torch.empty((B, H, NP + 1), dtype=torch.float32, device=q.device) if evidence else None
+        st = status_word(q.device)
+        rc = lib.capamd_duet_forward(_ptr(q), _ptr(d), _ptr(idf), B, Q, L, ctypes.byref(m), nb, _ptr(ws), ws.numel(), _ptr(out), _ptr(pt), _ptr(ev),
+                                     _ptr(st.t), _stream())
+        self._finish(rc, "capamd_duet_forward", st, check)
+        res = (out,) + ((pt,) if parts else ()) + ((ev[:, :, 0], ev[:, :, 1:]) if evidence else ())
+        return res if len(res) > 1 else out
+
+
 QUERY_SIDE, DOC_SIDE = 0, 1        # the `side` of the tower entries: which id-range bit a bad id sets
 
 

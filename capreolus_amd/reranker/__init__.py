@@ -149,5 +149,6 @@ from .POSITDRMM import POSITDRMM, POSITDRMM_basic, POSITDRMM_class  # noqa: E402
 from .DeepTileBar import DeepTileBar, DeepTileBar_class, DeepTileBar_nn  # noqa: E402,F401
 from .DSSM import DSSM, DSSM_class  # noqa: E402,F401
 from .CDSSM import CDSSM, CDSSM_class  # noqa: E402,F401
+from .DUET import DUET, DUET_class  # noqa: E402,F401
 
 registry = {"KNRM": KNRM, "DRMM": DRMM, "DRMMTKS": DRMMTKS, "PACRR": PACRR, "ConvKNRM": ConvKNRM, "ptBERTMaxP": PTBERTMaxP, "CEDRKNRM": CEDRKNRM}

@@ -614,6 +614,56 @@ int capamd_dssm_tower(const int64_t* indptr, const int* idx, const float* val, i
 int capamd_cos_sigmoid_pairs(const float* qrep, const float* drep, const int* pair_q, const int* pair_d, int64_t Nq, int64_t Nd, int64_t n_pairs, int R,
                              float* out, int* status, void* stream);
 
+/* ---- DUET (reference capreolus/reranker/DUET.py, DUET_class.forward) -------------------------------------------------------------------
+ * (added without a new CAPAMD_VERSION: purely additive, nothing existing changed)
+ * score = lm + dm per document, fp32 throughout; Q = 4 query terms, H = nfilters, M = lmhidden, act = relu (activation 0) or tanh (1).
+ *   local model        lm_x[h][q] = act(lm_b[h] + sum_d W[h][d] (q_ids[q] == d_ids[d]) idf[q])      (idf only with idfweight, else 1)
+ *                      lm = lm_w3 . act(lm_w0 flat(lm_x) + lm_b0) + lm_b3,  flat index h Q + q.
+ *                      Ids are compared as they are, without any mask: a pad in the query matches every pad in the document, and an id
+ *                      outside the table still matches an equal id.  The matching columns are added in ascending d.
+ *   distributed model  query:    qv = qf_w max_w act(q_b + conv_(3, dim)(emb[q_ids])[w]) + qf_b over the two windows w of three rows;
+ *                      document: c[h][t] = act(d_b1[h] + conv_(3, dim)(emb[d_ids])[h][t]),   t < L - 2
+ *                                p[h][t] = max(c[h][t .. t + 99]),                          t < L - 101 (exact)
+ *                                e[g][t] = act(d_b2[g] + sum_h d_w2[g][h] p[h][t])
+ *                                f[g]    = act(f1_b + sum_t f1_w[t] (qv[g] e[g][t])),        dm = f2_b + sum_g f2_w[g] f[g].
+ *                      The table is read as it is (row 0 is not forced to zero); an id outside [0, vocab) counts as a zero row in the
+ *                      distributed model and sets CAPAMD_STATUS_QUERY_ID_RANGE / _DOC_ID_RANGE; nothing is read outside the table.
+ * Every sum runs in an order that is a function of the document alone (no float atomics): a document's score does not depend on B, on its
+ * neighbours or on docs_per_microbatch, bit for bit.
+ * Two of the weights are re-laid out by the caller, once per set of weights: lm_wt [maxdoclen][H] is lm.conv.0.weight [H][1][1][maxdoclen]
+ * transposed (a position is one contiguous read of H floats); d_w1t [dim rounded up to 32][3 H rounded up to 16] holds
+ * dm.d_conv1.0.weight [H][1][3][dim] as d_w1t[k][j H + h] = w[h][j][k], the padding zeros, 16-byte aligned.  Everything else is read in
+ * place as nn.Linear / nn.Conv2d have it; emb [vocab][dim] 16-byte aligned.
+ * out fp32 [B]; parts_out (optional) fp32 [B][2] = (lm, dm); evidence_out (optional) fp32 [B][H][1 + (L - 101)]: per filter the query
+ * vector's entry qv[h], then the pooled row p[h][:].  idf fp32 [B][4] (may be NULL without idfweight).
+ * Limits (CAPAMD_ERR_ARG, nothing is launched; capamd_duet_workspace_bytes returns -1): Q == 4, 2 <= nfilters <= 32, 1 <= lmhidden <= 256,
+ * 1 <= dim <= 512, 103 <= L <= 8192, nhidden == L - 101, maxdoclen == L - outside the first four the reference itself does not run.
+ * workspace: capamd_duet_workspace_bytes(m, docs_per_microbatch, Q, L) bytes, 256-byte aligned: the per-token projections of a micro-batch
+ * (L x (3 H rounded up to 16) floats per document). */
+typedef struct capamd_duet_model {
+  const float* emb;                      /* [vocab][dim]        dm.embedding.weight */
+  const float* lm_wt;                    /* [maxdoclen][H]      lm.conv.0.weight, transposed (above) */
+  const float* lm_b;                     /* [H]                 lm.conv.0.bias */
+  const float *lm_w0, *lm_b0;            /* [M][4 H], [M]       lm.ffw.0 */
+  const float *lm_w3, *lm_b3;            /* [M], [1]            lm.ffw.3 */
+  const float *q_w, *q_b;                /* [H][3][dim], [H]    dm.q_conv.0 */
+  const float *qf_w, *qf_b;              /* [H][H], [H]         dm.q_ffw.0 */
+  const float* d_w1t;                    /* dm.d_conv1.0.weight, transposed and padded (above) */
+  const float* d_b1;                     /* [H]                 dm.d_conv1.0.bias */
+  const float *d_w2, *d_b2;              /* [H][H], [H]         dm.d_conv2.0 */
+  const float *f1_w, *f1_b;              /* [nhidden], [1]      dm.ffw_1.0 */
+  const float *f2_w, *f2_b;              /* [H], [1]            dm.ffw_2.1 */
+  int64_t vocab;
+  int dim, nfilters, lmhidden, maxdoclen, nhidden;
+  int activation;                        /* 0 relu, 1 tanh */
+  int idfweight;
+} capamd_duet_model;
+
+int64_t capamd_duet_workspace_bytes(const capamd_duet_model* m, int docs_per_microbatch, int Q, int L);   /* -1: refused geometry */
+int capamd_duet_forward(const int64_t* q_ids, const int64_t* d_ids, const float* idf, int B, int Q, int L, const capamd_duet_model* m,
+                        int docs_per_microbatch, void* workspace, int64_t workspace_bytes, float* out, float* parts_out, float* evidence_out,
+                        int* status, void* stream);
+
 /* ---- ConvKNRM ------------------------------------------------------------------------
  * Replaces ConvKNRM_class.forward, capreolus/reranker/ConvKNRM.py:42-77 (called from ConvKNRM.test :112-116).
  * The Conv1d layers (ConvKNRM.py:24-32) over the frozen embedding table (:17) are folded, once per model, into a table of
