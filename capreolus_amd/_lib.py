@@ -170,6 +170,9 @@ SIGNATURES = {
     "capamd_parade_workspace_bytes": (_i64, [_hp, _i, _i]),
     "capamd_parade_passage_cls": (_i, [_vp, _vp, _vp, _i, _i, _i, _mp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "capamd_parade_head": (_i, [_vp, _i, _i, _hp, _vp, _i64, _vp, _vp, _vp]),
+    "capamd_birch_workspace_bytes": (_i64, [_i, _i]),
+    "capamd_birch_plan": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "capamd_birch_head": (_i, [_vp, _i64, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "capamd_tk_workspace_bytes": (_i64, [_tp, _i, _i, _i]),
     "capamd_tk_forward": (_i, [_vp, _vp, _i, _i, _i, _tp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "capamd_hint_workspace_bytes": (_i64, [_hnp, _i, _i, _i]),

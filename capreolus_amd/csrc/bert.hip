@@ -7,7 +7,10 @@
 // Precision: the activation stream is 16-bit end to end (fp16 by default - the reference's autocast type - or
 // bf16, `compute_dtype` of the model); every accumulation, the residual sums (added in fp32 inside the LayerNorm
 // pass, one rounding), LayerNorm statistics, softmax and the pooler/classifier are fp32.  (A fp32 residual stream
-// was measured to give the same logit error: the error is set by the 16-bit GEMM operands.)
+// was measured to give the same logit error at BERT-base: there the error is set by the 16-bit GEMM operands.  On narrow, shallow
+// encoders it is not: at two layers of 128 the rounded residual cost 1.3 - 1.4 x the reference's autocast error, so models that are
+// not fused_capable - which run the separate-LayerNorm path anyway - keep an fp32 copy of the stream, Workspace::xf, as the residual
+// operand; the GEMMs still read the 16-bit one.)
 #include "bert_attn.h"
 #include "bert_gemm.h"
 #include "bert_gemm_ring16.h"
@@ -60,7 +63,8 @@ __global__ __launch_bounds__(256) void ln_kernel(const T* __restrict__ pre, cons
                                                  const float* __restrict__ pos, const float* __restrict__ type, int vocab,
                                                  int type_vocab, int S, const float* __restrict__ gamma,
                                                  const float* __restrict__ beta, int64_t M, int H,
-                                                 T* xb, int* status, int out_cm, float eps, int pos_pad_id, int max_pos) {
+                                                 T* xb, int* status, int out_cm, float eps, int pos_pad_id, int max_pos, float* xf) {
+  // xf (optional, row-major only): an fp32 copy of the stream - MODE 2 takes its residual from it, every mode leaves its output in it
   // one wave per token row, 8 elements (16 bytes of the 16-bit stream) per lane and step; H <= 1024
   using bf16x8 = typename Half<T>::x8;
   const int lane = threadIdx.x & 63;
@@ -114,7 +118,13 @@ __global__ __launch_bounds__(256) void ln_kernel(const T* __restrict__ pre, cons
         const bf16x8 b = reinterpret_cast<const bf16x8*>(pre + tok * H)[c];
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[i][e] = (float)b[e];
-        if (MODE == 2) {  // residual sum in fp32: projection output + the stream row it will replace
+        if (MODE == 2 && xf) {  // ... + the fp32 stream row (the residual is never rounded to 16 bits)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const float4 r = reinterpret_cast<const float4*>(xf + tok * H)[2 * c + h];
+            v[i][4 * h + 0] += r.x; v[i][4 * h + 1] += r.y; v[i][4 * h + 2] += r.z; v[i][4 * h + 3] += r.w;
+          }
+        } else if (MODE == 2) {  // residual sum in fp32: projection output + the stream row it will replace
           const bf16x8 r = reinterpret_cast<const bf16x8*>(xb + tok * H)[c];
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[i][e] += (float)r[e];
@@ -144,10 +154,13 @@ __global__ __launch_bounds__(256) void ln_kernel(const T* __restrict__ pre, cons
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const float4 g = reinterpret_cast<const float4*>(gamma)[2 * c + h], b = reinterpret_cast<const float4*>(beta)[2 * c + h];
-        ob[4 * h + 0] = (T)((v[i][4 * h + 0] - mean) * rstd * g.x + b.x);
-        ob[4 * h + 1] = (T)((v[i][4 * h + 1] - mean) * rstd * g.y + b.y);
-        ob[4 * h + 2] = (T)((v[i][4 * h + 2] - mean) * rstd * g.z + b.z);
-        ob[4 * h + 3] = (T)((v[i][4 * h + 3] - mean) * rstd * g.w + b.w);
+        const float4 y = make_float4((v[i][4 * h + 0] - mean) * rstd * g.x + b.x, (v[i][4 * h + 1] - mean) * rstd * g.y + b.y,
+                                     (v[i][4 * h + 2] - mean) * rstd * g.z + b.z, (v[i][4 * h + 3] - mean) * rstd * g.w + b.w);
+        ob[4 * h + 0] = (T)y.x;
+        ob[4 * h + 1] = (T)y.y;
+        ob[4 * h + 2] = (T)y.z;
+        ob[4 * h + 3] = (T)y.w;
+        if (xf) reinterpret_cast<float4*>(xf + tok * H)[2 * c + h] = y;
       }
       if (out_cm) *reinterpret_cast<bf16x8*>(xb + cm_offset(tok, c * 8, H)) = ob;   // chunk-major stream (bert_gemm.h)
       else reinterpret_cast<bf16x8*>(xb + tok * H)[c] = ob;
@@ -818,6 +831,7 @@ struct Workspace {
   float* part;    // [M][H/64][2]
   float* mu_x; float* rstd_x; float* mu_p; float* rstd_p;  // [M] each
   float2* mr_x; float2* mr_p;                              // [M] the same, interleaved
+  float* xf;      // [M, H] the stream in fp32: the residual operand of the separate-LayerNorm path; only for models that are not fused_capable (else null)
 };
 
 size_t ws_bytes_for(int H, int F, int S, int64_t n_psg_mb, int64_t n_psg_total) {
@@ -828,6 +842,7 @@ size_t ws_bytes_for(int H, int F, int S, int64_t n_psg_mb, int64_t n_psg_total) 
   add((size_t)M * H * 2); add((size_t)M * H * 2); add((size_t)M * F * 2); add((size_t)n_psg_total * 4); add(256);
   add((size_t)M * (H / 64) * 8); add((size_t)M * 4); add((size_t)M * 4); add((size_t)M * 4); add((size_t)M * 4);
   add((size_t)M * 8); add((size_t)M * 8);
+  if (!fused_capable(H, F)) add((size_t)M * H * 4);
   return b;
 }
 
@@ -848,6 +863,7 @@ Workspace carve(char* p, int H, int F, int S, int64_t n_psg_mb, int64_t n_psg_to
   w.mu_x = (float*)take((size_t)M * 4); w.rstd_x = (float*)take((size_t)M * 4);
   w.mu_p = (float*)take((size_t)M * 4); w.rstd_p = (float*)take((size_t)M * 4);
   w.mr_x = (float2*)take((size_t)M * 8); w.mr_p = (float2*)take((size_t)M * 8);
+  w.xf = fused_capable(H, F) ? nullptr : (float*)take((size_t)M * H * 4);
   return w;
 }
 
@@ -911,10 +927,11 @@ hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_
                          m->type_emb, m->vocab, m->type_vocab, S, m->emb_ln_g, m->emb_ln_b, H, (T*)w.xb, status, eps, m->pos_pad_id, m->max_pos);
     } else
       hipLaunchKernelGGL((ln_kernel<0, T>), dim3((unsigned)((M_real + 3) / 4)), dim3(256), 0, s, (const T*)nullptr, ids_mb, seg_mb, m->word_emb, m->pos_emb,
-                         m->type_emb, m->vocab, m->type_vocab, S, m->emb_ln_g, m->emb_ln_b, M_real, H, (T*)w.xb, status, 0, eps, m->pos_pad_id, m->max_pos);
+                         m->type_emb, m->vocab, m->type_vocab, S, m->emb_ln_g, m->emb_ln_b, M_real, H, (T*)w.xb, status, 0, eps, m->pos_pad_id, m->max_pos, w.xf);
     if (M > M_real) {   // (S % 32 == 0: the pad rows are whole 32-row groups, contiguous in the row-major and the chunk-major layout alike)
       (void)hipMemsetAsync(w.xb + M_real * H, 0, (size_t)(M - M_real) * H * 2, s);
       (void)hipMemsetAsync(w.ctx + M_real * H, 0, (size_t)(M - M_real) * H * 2, s);
+      if (w.xf && !fused) (void)hipMemsetAsync(w.xf + M_real * H, 0, (size_t)(M - M_real) * H * 4, s);
     }
     if (tap) cedr_tap_layer<T>(*tap, 0, (const T*)w.xb, mask_mb, seg_mb, p0, np, S, H, s, fused);   // (normalised in either layout)
     if (fused) {
@@ -967,7 +984,7 @@ hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_
           e = launch_gemm<kEpiBiasBf16, T>(g, s);
           if (e != hipSuccess) break;
           hipLaunchKernelGGL((ln_kernel<2, T>), dim3((unsigned)((npad + 3) / 4)), dim3(256), 0, s, (const T*)pre_c, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             0, 0, 1, ln1g, ln1b, npad, H, x_c, status, 0, eps, -1, 0);
+                             0, 0, 1, ln1g, ln1b, npad, H, x_c, status, 0, eps, -1, 0, (float*)nullptr);
           g.N = F; g.K = H; g.A = x_c; g.W = w1; g.bias = b1; g.out_bf16 = mid_c;
           e = launch_gemm<kEpiBiasGeluBf16, T>(g, s);
           if (e != hipSuccess) break;
@@ -981,7 +998,7 @@ hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_
             break;
           }
           hipLaunchKernelGGL((ln_kernel<2, T>), dim3((unsigned)((npad + 3) / 4)), dim3(256), 0, s, (const T*)pre_c, nullptr, nullptr, nullptr, nullptr, nullptr,
-                             0, 0, 1, ln2g, ln2b, npad, H, x_c, status, 0, eps, -1, 0);
+                             0, 0, 1, ln2g, ln2b, npad, H, x_c, status, 0, eps, -1, 0, (float*)nullptr);
           cls_done = true;
           cls_x = x_c;
           break;
@@ -1065,7 +1082,7 @@ hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_
       e = launch_gemm<kEpiBiasBf16, T>(g, s);
       if (e != hipSuccess) break;
       hipLaunchKernelGGL((ln_kernel<2, T>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, (const T*)w.pre, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         0, 0, S, ln1g, ln1b, M, H, (T*)w.xb, status, 0, eps, -1, 0);
+                         0, 0, S, ln1g, ln1b, M, H, (T*)w.xb, status, 0, eps, -1, 0, w.xf);
       // feed-forward: 768 -> 3072 (GELU) -> 768, residual + LayerNorm
       const bool cm = chunk_major_enabled() && pingpong_shape(M, F, H) && pingpong_shape(M, H, F);  // mid in the chunk-major layout (bert_gemm.h)
       g.A = w.xb; g.W = w1; g.bias = b1; g.N = F; g.K = H; g.out_bf16 = w.mid; g.out_cm = cm;
@@ -1078,7 +1095,7 @@ hipError_t encode_passages(const int64_t* ids, const int64_t* mask, const int64_
       g.a_cm = 0;
       if (e != hipSuccess) break;
       hipLaunchKernelGGL((ln_kernel<2, T>), dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, (const T*)w.pre, nullptr, nullptr, nullptr, nullptr, nullptr,
-                         0, 0, S, ln2g, ln2b, M, H, (T*)w.xb, status, 0, eps, -1, 0);
+                         0, 0, S, ln2g, ln2b, M, H, (T*)w.xb, status, 0, eps, -1, 0, w.xf);
       if (tap) cedr_tap_layer<T>(*tap, l + 1, (const T*)w.xb, mask_mb, seg_mb, p0, np, S, H, s);
     }
     if (e != hipSuccess) break;

@@ -1293,6 +1293,121 @@ class ParadeEngine:
         return (out, cls) if return_cls else out
 
 
+BIRCH_MAX_PASSAGES = 64      # a document's passages are the lanes of one wave (csrc/birch.hip)
+BIRCH_MAX_HIDDEN = 256
+BIRCH_TRUNCATE = {"none": 0, "reference": 1}
+
+
+class BirchEngine:
+    """Birch (reference birch.py:72-127) on top of a BertEngine whose pooler / classifier are BertForNextSentencePrediction's:
+    capamd_birch_plan (which passages are encoded, compacted, their masks cleared behind the sub-batch's cut) -> the passage encoder
+    over the compacted rows -> capamd_birch_head (fill, top-k, combine).
+
+    truncate = "reference": a passage is scored up to the cut the reference slices its sub-batch at (:106-109) - with the torch of
+    today the first token of segment B, so `[CLS] q [SEP] t1` is all the encoder sees; the cut depends on `subbatch`, the reference's
+    batch size.  truncate = "none": the whole passage, as the commented-out loop (:110-115) would have it."""
+
+    def __init__(self, bert_engine, truncate="reference"):
+        if truncate not in BIRCH_TRUNCATE:
+            raise ValueError(f"truncate must be one of {sorted(BIRCH_TRUNCATE)}; got {truncate!r}")
+        self.be = bert_engine
+        self.truncate = truncate
+        self._plan_ws = None
+
+    @staticmethod
+    def check_dims(P, S, topk, hidden, subbatch=1):
+        """the refusals of capamd_birch_plan / capamd_birch_head, by name, before any device work"""
+        if not 1 <= P <= BIRCH_MAX_PASSAGES:
+            raise ValueError(f"Birch scores 1 to {BIRCH_MAX_PASSAGES} passages per document (numpassages); got {P}")
+        if not 1 <= topk <= P:
+            raise ValueError(f"topk must lie in 1..numpassages = {P} (torch.topk over a document's passage scores, birch.py:81); got topk = {topk}")
+        if not 0 <= hidden <= BIRCH_MAX_HIDDEN:
+            raise ValueError(f"hidden must lie in 0..{BIRCH_MAX_HIDDEN}; got {hidden}")
+        if subbatch < 1:
+            raise ValueError(f"subbatch must be at least 1; got {subbatch}")
+        if S not in SUPPORTED_LENGTHS:
+            raise ValueError(f"unsupported passage length {S} (supported: multiples of 32 up to 256, 384, 512)")
+
+    def plan(self, ids, mask, seg, subbatch, truncate=None):
+        """int64 [B, P, S] x3 -> (enc_ids, enc_mask, enc_seg int64 [n_enc, S], doc_first int32 [B + 1]).  Reads n_enc back: the one host
+        round trip of a call before the encoder's own (the bucket sizes)."""
+        truncate = self.truncate if truncate is None else truncate
+        if truncate not in BIRCH_TRUNCATE:
+            raise ValueError(f"truncate must be one of {sorted(BIRCH_TRUNCATE)}; got {truncate!r}")
+        B, P, S = ids.shape
+        self.check_dims(P, S, 1, 0, subbatch)
+        _need_gpu(ids, mask, seg)
+        ids, mask, seg = _i64(ids), _i64(mask), _i64(seg)
+        dev = ids.device
+        if B == 0:
+            none = torch.empty((0, S), dtype=torch.int64, device=dev)
+            return none, none, none, torch.zeros(1, dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        need = lib.capamd_birch_workspace_bytes(B, P)
+        if need < 0:
+            raise ValueError(f"Birch: {B} documents of {P} passages are more than one call takes (B P < 2^31)")
+        if self._plan_ws is None or self._plan_ws.numel() < need or self._plan_ws.device != dev:
+            self._plan_ws = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        enc = [torch.empty((B * P, S), dtype=torch.int64, device=dev) for _ in range(3)]
+        doc_first = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        n_enc = torch.empty(1, dtype=torch.int32, device=dev)
+        rc = lib.capamd_birch_plan(_ptr(ids), _ptr(mask), _ptr(seg), B, P, S, int(subbatch), BIRCH_TRUNCATE[truncate], _ptr(self._plan_ws),
+                                   self._plan_ws.numel(), _ptr(enc[0]), _ptr(enc[1]), _ptr(enc[2]), _ptr(doc_first), _ptr(n_enc), _stream())
+        _lib.check(rc, "capamd_birch_plan")
+        n = int(n_enc.item())
+        return enc[0][:n], enc[1][:n], enc[2][:n], doc_first
+
+    def passage_logits(self, enc_ids, enc_mask, enc_seg, skip_padding=None, check=True):
+        """the compacted rows int64 [n, S] x3 -> fp32 [n]: logit 1 of the next-sentence head, by the MaxP encoder path (P = 1, "first")"""
+        n, S = enc_ids.shape
+        if n == 0:
+            return torch.empty(0, dtype=torch.float32, device=enc_ids.device)
+        shape = (n, 1, S)
+        return self.be.forward(enc_ids.view(shape), enc_mask.view(shape), enc_seg.view(shape), "first", return_passage_logits=True, check=check,
+                               skip_padding=skip_padding)[1]
+
+    @staticmethod
+    def head(logits, doc_first, B, P, topk, combine, details=False):
+        """capamd_birch_head: fp32 [n] logits of the compacted rows + doc_first -> fp32 [B] (details: also the top-k values [B, topk] and
+        the passage scores [B, P] in the reference's layout).  combine: the state_dict names of Birch_Class.combine (``combine.weight``, or
+        ``combine.0.*`` and ``combine.2.*``) -> live fp32 tensors on the device, read in place."""
+        keep = {k: _f32(v.detach()) for k, v in combine.items()}
+        logits = _f32(logits)
+        _need_gpu(logits, doc_first, *keep.values())
+        if "combine.weight" in keep:
+            hidden, w1, b1, w2, b2 = 0, keep["combine.weight"], None, None, None
+        else:
+            w1, b1, w2, b2 = (keep[k] for k in ("combine.0.weight", "combine.0.bias", "combine.2.weight", "combine.2.bias"))
+            hidden = w1.shape[0]
+        BirchEngine.check_dims(P, SUPPORTED_LENGTHS[0], topk, hidden)
+        if w1.numel() != max(hidden, 1) * topk:
+            raise ValueError(f"combine takes {w1.numel() // max(hidden, 1)} features, topk is {topk}")
+        dev = logits.device
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+        top = torch.empty((B, topk), dtype=torch.float32, device=dev) if details else None
+        scores = torch.empty((B, P), dtype=torch.float32, device=dev) if details else None
+        if B == 0:
+            return (out, top, scores) if details else out
+        rc = _lib.load().capamd_birch_head(_ptr(logits), logits.numel(), _ptr(_i32(doc_first)), B, P, topk, hidden, _ptr(w1), _ptr(b1), _ptr(w2),
+                                           _ptr(b2), _ptr(out), _ptr(top), _ptr(scores), _stream())
+        _lib.check(rc, "capamd_birch_head")
+        return (out, top, scores) if details else out
+
+    def forward(self, doc, mask, seg, topk, combine, subbatch=None, truncate=None, details=False, skip_padding=None, check=True):
+        """Birch_Class.forward (birch.py:72-83): int64 [B, P, S] x3 -> fp32 [B]; details: (out, top-k values [B, topk], passage scores
+        [B, P], the compacted rows' logits [n_enc], doc_first).  subbatch (default: B, what the reference uses): passages per
+        sub-batch under truncate = "reference"."""
+        B, P, S = doc.shape
+        hidden = 0 if "combine.weight" in combine else combine["combine.0.weight"].shape[0]
+        subbatch = max(B, 1) if subbatch is None else int(subbatch)
+        self.check_dims(P, S, topk, hidden, subbatch)
+        _need_gpu(doc, mask, seg)
+        enc_ids, enc_mask, enc_seg, doc_first = self.plan(doc, mask, seg, subbatch, truncate)
+        logits = self.passage_logits(enc_ids, enc_mask, enc_seg, skip_padding, check)
+        res = self.head(logits, doc_first, B, P, topk, combine, details)
+        return (*res, logits, doc_first) if details else res
+
+
 class _PerDocumentEngine:
     """What the engines of the per-document rerankers share: the documents of a call run in micro-batches of `docs_per_microbatch`
     (None: as many as the model's budget holds) on one workspace that only ever grows."""

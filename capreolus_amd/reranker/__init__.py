@@ -150,5 +150,6 @@ from .DeepTileBar import DeepTileBar, DeepTileBar_class, DeepTileBar_nn  # noqa:
 from .DSSM import DSSM, DSSM_class  # noqa: E402,F401
 from .CDSSM import CDSSM, CDSSM_class  # noqa: E402,F401
 from .DUET import DUET, DUET_class  # noqa: E402,F401
+from .birch import Birch, Birch_Class  # noqa: E402,F401
 
 registry = {"KNRM": KNRM, "DRMM": DRMM, "DRMMTKS": DRMMTKS, "PACRR": PACRR, "ConvKNRM": ConvKNRM, "ptBERTMaxP": PTBERTMaxP, "CEDRKNRM": CEDRKNRM}

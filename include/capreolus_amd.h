@@ -413,6 +413,36 @@ int capamd_parade_passage_cls(const int64_t* ids, const int64_t* mask, const int
 int capamd_parade_head(const float* cls_rows, int B, int P, const capamd_parade_head_model* hm, void* workspace, int64_t workspace_bytes,
                        float* out, float* aggregated_out, void* stream);
 
+/* ---- Birch (reference capreolus/reranker/birch.py, Birch_Class.forward / score_passages :72-127) ----------------------------------
+ * (added without a new CAPAMD_VERSION: purely additive, nothing existing changed)
+ * The passage scores are capamd_bert_maxp_forward's passage logits (BertForNextSentencePrediction is the pooler and a [2, hidden]
+ * classifier under another name; cls_w / cls_b = cls.seq_relationship).  Two calls stand around the encoder:
+ *  capamd_birch_plan: ids / mask / seg int64 [B][P][S] -> which passages are encoded and how (:92-109), per document:
+ *   valid[p] = #(seg + mask == 2) > 2, and valid[0] when no passage is valid; the valid passages keep their order (rank 0, 1, ...);
+ *   sub-batch g = the passages of rank g subbatch .. (g + 1) subbatch - 1; its cut = the largest, over its passages, of the FIRST
+ *   position of the maximum of seg + mask (what argmax returns: the first token of segment B where there is one).  truncate 1: the mask
+ *   of a passage is cleared behind its sub-batch's cut (the reference slices the sub-batch there; a key behind the cut gets no
+ *   weight either way); truncate 0: nothing is cleared and subbatch has no effect.
+ *   enc_ids / enc_mask / enc_seg int64 [B P][S]: rows 0 .. n_enc - 1 are written - the valid passages document after document, the
+ *   rows of document b at doc_first[b] .. doc_first[b + 1] - 1; doc_first int32 [B + 1] and n_enc int32 [1] on the device.
+ *   workspace: capamd_birch_workspace_bytes(B, P) bytes, 256-byte aligned.
+ *  capamd_birch_head: enc_logits fp32 [n_logits] (the encoder's logits of the n_logits = n_enc compacted rows) + doc_first -> per
+ *   document the P passage scores (its encoded logits, then their minimum for the passages that were not encoded, :121-125), the topk
+ *   largest in descending order (a selection: the values' own bits; equal values in any order; NaN ranks above everything and is the
+ *   minimum of a document that has one, as torch.topk / torch.min have it), and combine (:41-47, 82):
+ *     hidden == 0:  out[b] = sum_i w1[i] top[i]                        w1 = combine.weight [1][topk]; b1, w2, b2 unused
+ *     hidden  > 0:  out[b] = b2[0] + sum_j w2[j] relu(b1[j] + sum_i w1[j][i] top[i])     w1 = combine.0.weight [hidden][topk], w2 = combine.2.weight
+ *   read in place from the live fp32 tensors; sums in ascending i, the hidden units reduced in a fixed order: a document's score is a
+ *   function of its own logits alone.  topk_out (optional) [B][topk]; passage_scores_out (optional) [B][P].  A document whose
+ *   doc_first range is empty or leaves [0, n_logits) scores what lies inside it (0 for none); nothing is read outside enc_logits.
+ * Limits (CAPAMD_ERR_ARG, nothing is launched; capamd_birch_workspace_bytes returns -1): 1 <= topk <= P <= 64, 0 <= hidden <= 256,
+ * 1 <= subbatch, S a length of capamd_bert_maxp_forward (multiples of 32 up to 256, 384, 512), B P < 2^31, truncate 0 or 1. */
+int64_t capamd_birch_workspace_bytes(int B, int P);
+int capamd_birch_plan(const int64_t* ids, const int64_t* mask, const int64_t* seg, int B, int P, int S, int subbatch, int truncate, void* workspace,
+                      int64_t workspace_bytes, int64_t* enc_ids, int64_t* enc_mask, int64_t* enc_seg, int* doc_first, int* n_enc, void* stream);
+int capamd_birch_head(const float* enc_logits, int64_t n_logits, const int* doc_first, int B, int P, int topk, int hidden, const float* w1,
+                      const float* b1, const float* w2, const float* b2, float* out, float* topk_out, float* passage_scores_out, void* stream);
+
 /* ---- TK (reference capreolus/reranker/TK.py, TK_class.forward :124-143, called from TK.test) ------------------------------------
  * score[b] of query ids q_ids [B, Q] against document ids d_ids [B, L] (int64), fp32 throughout:
  *   x = emb[id] + pe[position]; numlayers post-norm TransformerEncoderLayers (ReLU, LayerNorm eps ln_eps, no dropout), the query and
