@@ -83,6 +83,14 @@ __device__ __forceinline__ float cos_pass(F val, int W, const float* qn, int i0,
   return den;
 }
 
+// c + a b with the product rounded before the sum.  (__fmul_rn / __fadd_rn are plain * and + in HIP's headers, and under hipcc's
+// default -ffp-contract=fast the pair became one fma: the idf sum of a document that matches two query terms was an ulp off.)
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return c + p;
+}
+
 // ---- stage 1 ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void front_kernel(const int64_t* __restrict__ q_ids, const float* __restrict__ q_idf, const int64_t* __restrict__ d_ids,
                                                     int Q, int L, const float* __restrict__ emb, int64_t V, int D, int Dp, int64_t pad, int64_t n,
@@ -155,7 +163,7 @@ __global__ __launch_bounds__(256) void front_kernel(const int64_t* __restrict__ 
       float widf = 0.f;
       for (int i = 0; i < Q; ++i) {          // in query order, the product and the sum each rounded as the reference's tensor arithmetic does
         em += cnt[i];
-        widf = __fadd_rn(widf, __fmul_rn((float)cnt[i], q_idf[b * Q + i]));
+        widf = mul_then_add((float)cnt[i], q_idf[b * Q + i], widf);
       }
       s0 = (float)((double)em / (double)len);
       s1 = widf / (float)len;

@@ -221,3 +221,217 @@ def yardstick(name, plugin_cls):
 def bound(e_ref, scale):
     """the tolerance of a quantity: max(4 e_ref, 16 fp32 ulp of its largest magnitude in the case)"""
     return max(4.0 * e_ref, 16.0 * float(np.spacing(np.float32(scale))))
+
+
+# ---- the geometry sweep (tests/test_gpu_posit_geometry.py): points without a recorded reference ------------------------------------------
+QUANTITIES = ("score", "features", "query_context", "doc_context")
+_sweeps = {}
+
+
+def sweep_ids(rs, B, Q, L, v=V):
+    """int64 query ids [B, Q] and document ids [B, L] for B >= 2 and any Q <= 16, with the patterns check_sweep_ids asserts (pair i
+    stands for pair i % B):
+    pair 0: exact matches at both ends of the document (with L >= 12 the first query term three times);
+    pair 1: a pad query term at Q - 1 - in the LAST group of four query terms - against a document with two trailing pads;
+    pair 2: the tiny-norm row in the document (and in the query if Q > 2); the first query term again at the head of the last group of
+            four (Q > 4; at Q - 1 below that) and, with Q > 8, term 3 again at 6; with L >= 12 that term seven times in the document;
+    pair 3: a pad inside the document which a query bigram spans."""
+    assert B >= 2 and L >= 5 and 1 <= Q <= 16, (B, Q, L)
+    q = rs.randint(1, v, size=(B, Q)).astype(np.int64)
+    d = rs.randint(1, v, size=(B, L)).astype(np.int64)
+    q[q == TINY_TOKEN] = TINY_TOKEN + 1
+    b0, b1, b2, b3 = (i % B for i in range(4))
+    last = 4 * ((Q - 1) // 4)
+    if Q > 1:
+        q[b1, Q - 1] = 0
+        q[b2, last if Q > 4 else Q - 1] = q[b2, 0]
+    if Q > 2:
+        q[b2, 1] = TINY_TOKEN
+    if Q > 8:
+        q[b2, 6] = q[b2, 3]
+    d[b3, 2] = 0
+    if Q > 1:
+        d[b3, 1], d[b3, 3] = q[b3, 0], q[b3, 1]
+    d[b0, 0], d[b0, L - 1] = q[b0, 0], q[b0, Q - 1]
+    if L >= 12:
+        d[b0, 4], d[b0, 6] = q[b0, 0], q[b0, 0]
+    d[b2, 1] = TINY_TOKEN
+    if L >= 12:
+        d[b2, 2:9] = q[b2, 0]
+    d[b1, L - 2:] = 0
+    return q, d
+
+
+def check_sweep_ids(q, d):
+    """the patterns the sweep relies on"""
+    B, Q = q.shape
+    L = d.shape[1]
+    b0, b1, b2, b3 = (i % B for i in range(4))
+    last = 4 * ((Q - 1) // 4)
+    assert ((d != 0).sum(1) >= 2).all()
+    assert (d[b1, L - 2:] == 0).all() and d[b1, L - 3] != 0                 # a document with trailing pads
+    assert (d[b2] == TINY_TOKEN).any() and d[b0, 0] == q[b0, 0] != 0 and d[b3, 2] == 0
+    assert not (q[:, [i for i in range(Q) if i != 1]] == TINY_TOKEN).any()
+    if Q > 1:
+        assert q[b1, Q - 1] == 0 and (q[b1, :Q - 1] != 0).all()            # one pad query term, in the last group of four
+        assert q[b2, 0] != 0 and (q[b2] == q[b2, 0]).sum() >= 2
+    if Q > 4:
+        assert Q - 1 >= last >= 4 and q[b2, last] == q[b2, 0]              # a term repeated across two groups of four
+    if Q > 8:
+        assert q[b2, 6] == q[b2, 3] != 0
+    if L >= 12:
+        assert (d[b2] == q[b2, 0]).sum() >= 7
+
+
+def sweep_case(D, Q, L, B):
+    """a point of the sweep, everything from one RandomState seeded by the point: the table (make_embeddings), the weights
+    (make_weights), the ids (sweep_ids), idf [B, Q], extras [B, 4] (its last column doubles as the searcher's score, `bm25`).  Made
+    once per point, shared, left alone."""
+    key = (D, Q, L, B)
+    if key not in _sweeps:
+        rs = np.random.RandomState((D * 1000003 + Q * 10007 + L * 101 + B) % (1 << 31))
+        ex = SimpleNamespace(embeddings=make_embeddings(rs, d=D), pad=0, config={})
+        w = make_weights(rs, D)
+        q, d = sweep_ids(rs, B, Q, L)
+        idf, extras = (rs.rand(B, Q) * 3.0).astype(np.float32), (rs.rand(B, 4) * 2.0).astype(np.float32)
+        _sweeps[key] = dict(point=key, ex=ex, w=w, query=q, posdoc=d, query_idf=idf, extras=extras, bm25=extras[:, 3].copy())
+    return _sweeps[key]
+
+
+def sweep_yardstick(case, plugin_cls):
+    """(float64 restatement per quantity, e_ref per quantity = max |fp32 restatement - float64|) of a sweep_case (or a lane_case) - the
+    fp32 restatement reproduces the reference bit for bit on every fixture (tests/test_posit_cpu.py).  Computed once per case."""
+    import torch
+
+    if "yardstick" not in case:
+        host = build_from(case["ex"], case["w"], plugin_cls)[1].eval()
+        t = [torch.from_numpy(case[k]) for k in ("posdoc", "query", "query_idf", "extras")]
+        with torch.no_grad():
+            s64, d64 = host._forward_aten(*t, dtype=torch.float64, return_details=True)
+            s32, d32 = host._forward_aten(*t, return_details=True)
+        f64 = {"score": s64.numpy(), **{k: d64[k].numpy() for k in QUANTITIES[1:]}}
+        f32 = {"score": s32.numpy(), **{k: d32[k].numpy() for k in QUANTITIES[1:]}}
+        case["yardstick"] = (f64, {k: float(np.abs(f32[k] - f64[k]).max()) for k in QUANTITIES})
+    return case["yardstick"]
+
+
+def matching_case():
+    """(query ids [40, 16], document ids [40, 23], idf, searcher scores): ids from six tokens with pads anywhere (two leading document
+    terms kept), so that every query term matches several times and bigrams are frequent - the idf sum has sixteen non-zero products"""
+    rs = np.random.RandomState(16)
+    q, d = rs.randint(0, 6, size=(40, 16)).astype(np.int64), rs.randint(0, 6, size=(40, 23)).astype(np.int64)
+    d[:, :2] = rs.randint(1, 6, size=(40, 2))
+    return q, d, (rs.rand(40, 16) * 3).astype(np.float32), rs.rand(40).astype(np.float32)
+
+
+def fused_idf_stat(query_idf, query, doc, pad=0):
+    """the second match statistic as a kernel gives it that fuses each product into the running sum (one rounding per term, where the
+    reference rounds the product and the sum): what loop_stats' column 1 must NOT be confused with"""
+    out = np.zeros(doc.shape[0], dtype=np.float32)
+    for b in range(doc.shape[0]):
+        cleaned = [t for t in doc[b] if t != pad]
+        widf = np.float32(0.0)
+        for i, word in enumerate(query[b]):
+            widf = np.float32(float(sum(1 for t in cleaned if t == word)) * float(query_idf[b, i]) + float(widf))     # exact in float64
+        out[b] = widf / np.float32(len(cleaned))
+    return out
+
+
+# ---- the top-5 of one lane -------------------------------------------------------------------------------------------------------------
+LANE_POINT = (24, 4, 400, 3)
+LANE_VARIANTS = ("ascending", "descending", "ties", "decoy")
+LANE_SLOTS = 7 + 64 * np.arange(6)                     # six positions of lane 7 of the wave that pools the row
+DECOY_TOP = np.array([3, 74, 148, 225, 306])           # lanes 3, 10, 20, 33, 50
+DECOY_REST = 3 + 64 * np.arange(1, 6)                  # lane 3 again: behind its head, the 6th .. 10th largest of the row
+_lanes = {}
+
+
+def cosines(emb, qtok, toks):
+    """M_cos of one query token against tokens, in float64 as the model forms it (1e-7 added to each norm)"""
+    e = np.asarray(emb, dtype=np.float64)
+    qv = e[qtok] / (np.linalg.norm(e[qtok]) + 1e-7)
+    dv = e[toks] / (np.linalg.norm(e[toks], axis=-1, keepdims=True) + 1e-7)
+    return dv @ qv
+
+
+def lane_case(variant):
+    """LANE_POINT with the document of pair 0 rebuilt around the table's ranking by cosine against q[0, 0] (rank 0 is that token
+    itself): filled from rank 20 and below, then
+    ascending   the six best at LANE_SLOTS in ascending order of cosine - every arrival is the lane's new maximum;
+    descending  the same six in descending order - every arrival enters at the tail, the sixth is dropped;
+    ties        the query token at all six - six equal maxima in one lane;
+    decoy       the five best in five lanes (DECOY_TOP), the 6th .. 10th best all behind the first of them (DECOY_REST)."""
+    if variant not in _lanes:
+        base = sweep_case(*LANE_POINT)
+        emb, qtok, L = base["ex"].embeddings, int(base["query"][0, 0]), LANE_POINT[2]
+        order = np.argsort(-cosines(emb, qtok, np.arange(V)), kind="stable")
+        assert order[0] == qtok
+        d = base["posdoc"].copy()
+        d[0] = np.random.RandomState(400 + LANE_VARIANTS.index(variant)).choice(order[20:], size=L)
+        if variant == "ascending":
+            d[0, LANE_SLOTS] = order[:6][::-1]
+        elif variant == "descending":
+            d[0, LANE_SLOTS] = order[:6]
+        elif variant == "ties":
+            d[0, LANE_SLOTS] = qtok
+        else:
+            d[0, DECOY_TOP], d[0, DECOY_REST] = order[:5], order[5:10]
+        _lanes[variant] = dict({k: v for k, v in base.items() if k != "yardstick"}, posdoc=d, point=LANE_POINT + (variant,))
+    return _lanes[variant]
+
+
+def lane_row(case):
+    """(the float64 cosine row of pair 0's first query term, its positions from the largest down - equal entries in order of position)"""
+    row = cosines(case["ex"].embeddings, int(case["query"][0, 0]), case["posdoc"][0])
+    return row, np.argsort(-row, kind="stable")
+
+
+def check_lane(case, feature_bound):
+    """What makes a lane variant a test of the per-lane top-5, on float64 alone.  ascending / descending / ties: the six largest of the
+    row sit in ONE lane (positions congruent mod 64), and a fifth of the gap between the 5th and the 6th largest is more than 1000
+    feature bounds - for `ties`, whose six largest are equal by construction, the gap is taken from them to the 7th largest.  A lane
+    that kept four, or a pop in a wrong lane, then misses the mean of the top 5 by orders of magnitude.  decoy: the five largest in
+    five lanes, the 6th .. 10th in the lane of the largest, the same margin between the 5th and the 6th."""
+    variant = case["point"][-1]
+    row, top = lane_row(case)
+    v = row[top]
+    print(f"\nlane {variant}: positions {top[:10].tolist()} values {np.round(v[:10], 4).tolist()} feature bound {feature_bound:.3g}")
+    if variant == "decoy":
+        assert len(set((top[:5] % 64).tolist())) == 5 and set((top[5:10] % 64).tolist()) == {int(top[0]) % 64}
+        assert (v[4] - v[5]) / 5 > 1000 * feature_bound and v[9] > v[10]
+        return
+    assert len(set((top[:6] % 64).tolist())) == 1 and sorted(top[:6].tolist()) == LANE_SLOTS.tolist()
+    if variant == "ties":
+        assert v[0] == v[5]
+    else:
+        assert (v[4] - v[5]) / 5 > 1000 * feature_bound
+        assert top[:6].tolist() == (LANE_SLOTS[::-1] if variant == "ascending" else LANE_SLOTS).tolist()
+    assert (v[5] - v[6]) / 5 > 1000 * feature_bound
+
+
+# ---- the chunks of steps (posit.hip: chunk_steps, carve) ----------------------------------------------------------------------------------
+PROJ_BYTES = 512 << 20
+# (D, Q, L of the base pairs, pairs in the one micro-batch) -> (T, the query side's chunks, the document side's chunks), rec_kernel<NB>
+CHUNK_POINTS = {
+    "three_chunks_gemm_tile_3": ((150, 4, 200, 1000), (87, [4], [87, 87, 26]), 3),
+    "three_chunks_widest": ((300, 4, 120, 1000), (52, [4], [52, 52, 16]), 5),
+    "chunked_query_one_step": ((24, 16, 5, 16400), (15, [15, 1], [5]), 1),
+}
+CHUNK_BASE_PAIRS = 5
+
+
+def chunk_steps(n, D, Q, L):
+    """positions per chunk of the recurrence for a micro-batch of n pairs, as posit.hip's chunk_steps"""
+    Dp = (D + 63) // 64 * 64
+    return int(min(max(PROJ_BYTES // (n * 8 * Dp * 4), 1), max(L, Q)))
+
+
+def chunks(S, T):
+    return [min(T, S - s0) for s0 in range(0, S, T)]
+
+
+def workspace_bytes(n, D, Q, L, T):
+    """posit.hip's carve for chunks of T steps: 4-byte cells, every buffer rounded up to 256 bytes"""
+    Dp, S = (D + 63) // 64 * 64, max(L, Q)
+    cells = (L * n * Dp, Q * n * Dp, S * n * 2 * Dp, L * n * 2 * Dp, Q * n * 2 * Dp, T * n * 8 * Dp, 2 * n * Dp, n * Q * L, n * Q * L, n * 4)
+    return sum((4 * c + 255) // 256 * 256 for c in cells)

@@ -8,7 +8,12 @@ own fp32 error on that case (posit_case.yardstick).  Every figure is printed bef
 Which case reaches which instantiation of the launcher (rec_kernel<NB>, NB = padded width / 64; the sequence tile is 16 everywhere):
 NB = 1: every fixture of dim 24; NB = 5: posit_dim300 (17 pairs: a full tile and a ragged second one); NB = 2, 3, 4: WIDTHS below.  The
 projection GEMM's column tiles: 4 NB % 3 == 0 only at NB = 3 (gemm_kernel<2, 3>), gemm_kernel<2, 2> at the others.  More than one chunk
-of steps per layer: test_chunked_steps_give_the_same_bits."""
+of steps per layer: test_chunked_steps_give_the_same_bits (two chunks at NB = 1).
+
+Every case here has Q <= 4, pad columns in its width and at most one of a row's five largest per lane of the pooling wave.  The rest of
+the geometry - Q = 5 .. 16, document lengths around 64 / 128 / 320 and at 8192, widths with Dp == D at every NB, six candidates in one
+lane, batches around the sequence tile, three chunks at NB = 3 and 5 and a chunked query side - is in tests/test_gpu_posit_geometry.py,
+whose docstring says which point reaches which instantiation."""
 import numpy as np
 import pytest
 import torch

@@ -158,6 +158,95 @@ def test_match_statistics_on_random_ids_with_pads_anywhere():
     assert np.array_equal(got, posit_case.loop_stats(idf, q, d))
 
 
+# ---- the preconditions of the geometry sweep (tests/test_gpu_posit_geometry.py) -----------------------------------------------------------
+SWEEP_POINTS = ([(24, Q, 40, 5) for Q in (1, 2, 4, 5, 6, 7, 8, 9, 12, 13, 15, 16)] + [(300, 16, 40, 17), (24, 5, 5, 3), (24, 5, 321, 3), (24, 4, 8192, 2),
+                (1, 5, 17, 3), (320, 5, 17, 3), (64, 5, 17, 33)] + [p[:3] + (posit_case.CHUNK_BASE_PAIRS,) for p, _, _ in posit_case.CHUNK_POINTS.values()])
+
+
+@pytest.mark.parametrize("D,Q,L,B", SWEEP_POINTS)
+def test_sweep_case_draws_the_id_patterns_it_promises(D, Q, L, B):
+    c = posit_case.sweep_case(D, Q, L, B)
+    q, d = c["query"], c["posdoc"]
+    posit_case.check_sweep_ids(q, d)
+    assert posit_case.sweep_case(D, Q, L, B) is c                                     # made once
+    assert q.shape == (B, Q) and d.shape == (B, L) and q.dtype == d.dtype == np.int64 and q.max() < posit_case.V and d.max() < posit_case.V
+    assert c["query_idf"].shape == (B, Q) and c["extras"].shape == (B, 4) and np.array_equal(c["bm25"], c["extras"][:, 3])
+    emb = c["ex"].embeddings
+    assert emb.shape == (posit_case.V, D) and not emb[0].any() and 0.5e-7 < np.linalg.norm(emb[posit_case.TINY_TOKEN]) < 2e-7
+    if Q > 4:
+        # the pad query term and the repeated one sit in the last group of four, which a later pass of cos_pass handles
+        assert (np.nonzero(q[1 % B] == 0)[0] >= 4 * ((Q - 1) // 4)).all()
+        assert q[2 % B, 4 * ((Q - 1) // 4)] == q[2 % B, 0]
+    stats = posit_case.loop_stats(c["query_idf"], q, d)
+    host = torch.cat(exact_match_stats(torch.from_numpy(c["query_idf"]), torch.from_numpy(q), torch.from_numpy(d), 0), dim=1).numpy()
+    assert np.array_equal(stats, host)
+
+
+def test_sweep_yardstick_is_the_restatements_own_error():
+    c = posit_case.sweep_case(24, 9, 40, 5)
+    f64, e_ref = posit_case.sweep_yardstick(c, POSITDRMM)
+    assert posit_case.sweep_yardstick(c, POSITDRMM)[0] is f64 and set(f64) == set(e_ref) == set(posit_case.QUANTITIES)
+    for k in posit_case.QUANTITIES:
+        scale = np.abs(f64[k]).max()
+        print(f"\n(24, 9, 40, 5) {k}: e_ref {e_ref[k]:.3g} scale {scale:.3g} bound {posit_case.bound(e_ref[k], scale):.3g}")
+        assert f64[k].dtype == np.float64 and 0 < e_ref[k] <= 1e-4 * scale, (k, e_ref[k], scale)
+    assert f64["features"].shape == (5, 9, 6) and f64["doc_context"].shape == (5, 40, 48)
+
+
+@pytest.mark.parametrize("variant", posit_case.LANE_VARIANTS)
+def test_lane_variants_put_six_candidates_into_one_lane(variant):
+    """the preconditions of test_top5_of_one_lane, on float64 alone (posit_case.check_lane)"""
+    c = posit_case.lane_case(variant)
+    f64, e_ref = posit_case.sweep_yardstick(c, POSITDRMM)
+    b = posit_case.bound(e_ref["features"], np.abs(f64["features"]).max())
+    posit_case.check_lane(c, b)
+    row, top = posit_case.lane_row(c)
+    # the float64 restatement pools that row: its max and the mean of its five largest
+    assert abs(f64["features"][0, 0, 0] - row[top[0]]) < 1e-12 and abs(f64["features"][0, 0, 1] - row[top[:5]].sum() / 5) < 1e-12
+    assert ((c["posdoc"] != 0).sum(1) >= 2).all() and c["posdoc"].shape == (3, 400)
+    if variant == "ties":
+        assert f64["features"][0, 0, 5] == 1.0 and (c["posdoc"][0] == c["query"][0, 0]).sum() == 6
+    # a lane that kept four of its six would give (for the first three variants) the 7th largest in place of the 5th
+    if variant != "decoy":
+        assert (row[top[4]] - row[top[6]]) / 5 > 1000 * b
+
+
+def test_chunk_arithmetic_of_the_chunk_points():
+    """the chunk lengths the GPU tests claim follow from posit.hip's chunk_steps, and the library's workspace is the one carve lays out
+    for that T - one step more or less per chunk is another size (no device access)"""
+    lib = _lib.load()
+    for name, ((D, Q, L, n), (T, q_chunks, d_chunks), NB) in posit_case.CHUNK_POINTS.items():
+        assert posit_case.chunk_steps(n, D, Q, L) == T and (D + 63) // 64 == NB, name
+        assert posit_case.chunks(Q, T) == q_chunks and posit_case.chunks(L, T) == d_chunks, name
+        assert sum(q_chunks) == Q and sum(d_chunks) == L and max(len(q_chunks), len(d_chunks)) >= 2
+        m = _lib.PositModel()
+        m.vocab, m.pad, m.dim = posit_case.V, 0, D
+        got = lib.capamd_posit_workspace_bytes(ctypes.byref(m), n, Q, L)
+        assert got == posit_case.workspace_bytes(n, D, Q, L, T), (name, got)
+        assert got not in (posit_case.workspace_bytes(n, D, Q, L, T - 1), posit_case.workspace_bytes(n, D, Q, L, T + 1))
+        # the five base pairs run in one chunk per side
+        T0 = posit_case.chunk_steps(posit_case.CHUNK_BASE_PAIRS, D, Q, L)
+        assert posit_case.chunks(Q, T0) == [Q] and posit_case.chunks(L, T0) == [L]
+    assert posit_case.CHUNK_POINTS["three_chunks_gemm_tile_3"][1:] == ((87, [4], [87, 87, 26]), 3)       # 4 NB % 3 == 0: gemm_kernel<2, 3>
+    assert posit_case.CHUNK_POINTS["three_chunks_widest"][1:] == ((52, [4], [52, 52, 16]), 5)
+    assert posit_case.CHUNK_POINTS["chunked_query_one_step"][1][1] == [15, 1]
+    # the fixture test of two chunks (test_chunked_steps_give_the_same_bits): 655 + 145
+    assert posit_case.chunks(800, posit_case.chunk_steps(400, 24, 4, 800)) == [655, 145]
+
+
+def test_matching_case_tells_a_fused_idf_sum_from_the_references():
+    q, d, idf, bm25 = posit_case.matching_case()
+    loops = posit_case.loop_stats(idf, q, d)
+    host = torch.cat(exact_match_stats(torch.from_numpy(idf), torch.from_numpy(q), torch.from_numpy(d), 0), dim=1).numpy()
+    assert np.array_equal(host, loops) and (loops > 0).all() and ((d != 0).sum(1) >= 2).all()
+    fused = posit_case.fused_idf_stat(idf, q, d)
+    print(f"\npairs whose idf statistic a fused multiply-add rounds differently: {int((fused != loops[:, 1]).sum())} of {len(fused)}")
+    assert (fused != loops[:, 1]).sum() >= 3 and np.abs(fused - loops[:, 1]).max() <= 2 * np.spacing(loops[:, 1].max())
+    # ... and the sweep point that found it: pair 2 of (24, 7, 40, 5), whose query repeats a term the document holds seven times
+    c = posit_case.sweep_case(24, 7, 40, 5)
+    assert posit_case.fused_idf_stat(c["query_idf"], c["query"], c["posdoc"])[2] != posit_case.loop_stats(c["query_idf"], c["query"], c["posdoc"])[2, 1]
+
+
 def test_refusals():
     c = posit_case.load("posit_small")
     r, m = _model("posit_small")
